@@ -5,6 +5,8 @@
     python bench.py --mode train | transformer | detect      (configs 2 / 5, 3, 4 - their own lines)
 
 The timed region (exactly K steps between barrier + synchronize) is run --repeats times; `value` is the median.
+`--dump-outputs DIR` writes what the last timed step returned as DIR/<name>.npy; inputs are seeded, so two builds can be
+compared output for output with the same arguments.
 
 One "step" = one pass of the hot path (OPNet.forward through libopnet_hip.so) over one batch of `--batch` synthetic CATER
 clips (300 frames x 15 slots x 6 features, fp32) that is already resident in HBM, followed by the device-side
@@ -124,8 +126,9 @@ def accuracy_block(dev):
 def inference_from_files_block(n_clips=4096, threads=12):
     """What a user of the inference driver gets (outside the timed region): `n_clips` synthetic <video>.pkl + <video>_bb.json on
     local disk -> reasoning_inference_main (native clip-file reader into pinned buffers, ReasonerServer, int32 post-process, IoU)
-    at the reference's 12 workers (configs/inference_config.json: num_workers 12, batch_size 16).  cold: first pass after the page
-    cache was dropped (null when this process may not drop it); warm: the best of the three passes after it (every pass listed)."""
+    at the reference's 12 workers (configs/inference_config.json: num_workers 12, batch_size 16).  cold: null - dropping the page
+    cache is a host-wide setting, and the bench changes no host setting; warm: the best of the three passes after the first
+    (every pass listed)."""
     import pickle
     import tempfile
     from objectpermanence_amd.inference_main import reasoning_inference_main
@@ -145,14 +148,6 @@ def inference_from_files_block(n_clips=4096, threads=12):
         json.dump(CFG, open(os.path.join(tmp, "model.json"), "w"))
         json.dump({"batch_size": 16, "num_workers": threads, "device": "cuda:0", "model_path": os.path.join(tmp, "opnet.pth"),
                    "videos_dir": "unused", "sample_dir": sdir, "labels_dir": ldir}, open(os.path.join(tmp, "infer.json"), "w"))
-        dropped = False
-        try:
-            os.sync()
-            with open("/proc/sys/vm/drop_caches", "w") as f:
-                f.write("3\n")
-            dropped = True
-        except OSError:
-            pass
         rates = []
         for _ in range(4):
             t0 = time.perf_counter()
@@ -160,7 +155,7 @@ def inference_from_files_block(n_clips=4096, threads=12):
                                            os.path.join(tmp, "model.json"), write_files=False)
             rates.append((n_clips / (time.perf_counter() - t0), res["timing"]["steady_clips_per_s"]))
     return {"inference_from_files": {"clips": n_clips, "threads": threads, "batch_size": 16,
-                                     "clips_per_s_cold": round(rates[0][0], 1) if dropped else None,
+                                     "clips_per_s_cold": None,
                                      "clips_per_s_warm": round(max(r[0] for r in rates[1:]), 1),
                                      "steady_clips_per_s_warm": round(max(r[1] for r in rates[1:]), 1),
                                      "clips_per_s_by_pass": [round(r[0], 1) for r in rates],
@@ -171,8 +166,10 @@ def inference_from_files_block(n_clips=4096, threads=12):
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=200)
-    ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=None,
+                    help="timed steps per repeat (default 200; --mode transformer 4096, --exact 256; --mode detect 10)")
+    ap.add_argument("--warmup", type=int, default=None,
+                    help="untimed steps before them (default 20; --mode transformer 512, --exact 32; --mode detect 2)")
     ap.add_argument("--batch", type=int, default=None,
                     help="clips per GPU per step (default 32, the BASELINE configs); frames per pass for --mode detect (default 16)")
     ap.add_argument("--global-batch", type=int, default=None,
@@ -204,9 +201,36 @@ def parse():
     ap.add_argument("--repeats", type=int, default=15,
                     help="the timed region (exactly --steps steps between barrier + synchronize) is run this many times; the line "
                          "reports the MEDIAN (value_min / value_max alongside): one 5 ms region is box-to-box noise")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned in its last step as DIR/<name>.npy "
+                         "(float32 / float64, rank 0, at most 64 MB: a seeded sample of rows beyond that)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="target wall time of the CPU baseline sample")
     return ap.parse_args()
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(directory, arrays):
+    """--dump-outputs: every array of `arrays` (name -> tensor) as `directory`/<name>.npy, so that two builds can be compared output
+    for output on the same seeded inputs.  float64 stays float64, other floats become float32, integers float64 (exact below
+    2^53).  When the arrays hold more than DUMP_MAX_BYTES, each keeps a fixed seeded sample of its leading-axis rows, and the row
+    indices kept are written next to it as <name>.rows.npy."""
+    host = {}
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
+        host[name] = a.astype(np.float64 if a.dtype == np.float64 or a.dtype.kind in "biu" else np.float32)
+    total = sum(a.nbytes for a in host.values())
+    with_rows = sum(a.nbytes + 8 * (a.shape[0] if a.ndim else 0) for a in host.values())
+    os.makedirs(directory, exist_ok=True)
+    for name, a in host.items():
+        if total > DUMP_MAX_BYTES and a.ndim > 0:
+            keep = max(1, a.shape[0] * DUMP_MAX_BYTES // with_rows)
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], size=keep, replace=False))
+            a = a[rows]
+            np.save(os.path.join(directory, f"{name}.rows.npy"), rows.astype(np.float64))
+        np.save(os.path.join(directory, f"{name}.npy"), a)
 
 
 def cpu_baseline(boxes_np, params, seconds):
@@ -278,6 +302,9 @@ def bench_train(args, model, boxes, labels, world, rank, dev, dist, params):
     if step_aborted(model):
         raise SystemExit("bench: a persistent launch of a training step aborted; no line is printed for such a run")
     comm_ms = sum(a.elapsed_time(b) for a, b in comm_events) / max(len(comm_events), 1) if comm_events else None
+    if rank == 0 and args.dump_outputs:
+        # what a caller of train_step has after the last step: the loss it returned and the weights it updated in place
+        dump_outputs(args.dump_outputs, {"loss": loss, **{f"param.{n}": p for n, p in model.named_parameters()}})
     if rank == 0:
         from objectpermanence_amd import _lib
         x4_ok = (os.environ.get("OPNET_XCD4", "1") != "0"
@@ -518,6 +545,11 @@ def bench_detect(args, world, rank, dev, dist):
         tt = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
+    if rank == 0 and args.dump_outputs:
+        # the last pass's detections of all frames, concatenated; `frame` says which frame each row belongs to
+        dets = {k: torch.cat([o[k] for o in out]) for k in ("boxes", "scores", "labels")}
+        dets["frame"] = torch.cat([torch.full((len(o["scores"]),), i) for i, o in enumerate(out)])
+        dump_outputs(args.dump_outputs, dets)
     if rank == 0:
         fl, fl_exec, n_wino = detector_flops_per_frame(frames_per_pass=nf)
         tf = fl * nf * args.steps / elapsed / 1e12
@@ -844,6 +876,8 @@ def bench_transformer(args, world, rank, dev, dist):
         dist.destroy_process_group()
     if rank != 0:
         return
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"y": last["y"][-1]})
     R = max(1, args.repeats)
     passes = (server.forwards - f0) // R
     S, E = B * T_FRAMES, E_TX
@@ -1040,14 +1074,17 @@ def main():
     if args.mode == "transformer":
         # exact: sixteen passes of 16 one-clip requests; throughput: sixteen passes of 256 (a region starts with the GPU idle while the
         # host submits the first pass's 256 requests - ~1.1 ms - which four passes per region would charge at 0.28 ms a pass)
-        if args.steps == 200:
-            args.steps, args.warmup = (256, 32) if args.exact else (4096, 512)
+        steps, warmup = (256, 32) if args.exact else (4096, 512)
+        args.steps = steps if args.steps is None else args.steps
+        args.warmup = warmup if args.warmup is None else args.warmup
         return bench_transformer(args, world, rank, dev, dist)
     if args.mode == "detect":
         args.batch = args.batch or 16     # frames per pass
-        if args.steps == 200:
-            args.steps, args.warmup = 10, 2
+        args.steps = 10 if args.steps is None else args.steps
+        args.warmup = 2 if args.warmup is None else args.warmup
         return bench_detect(args, world, rank, dev, dist)
+    args.steps = 200 if args.steps is None else args.steps
+    args.warmup = 20 if args.warmup is None else args.warmup
 
     from objectpermanence_amd import ModelsFactory
     from synthdata import opnet as synth
@@ -1082,7 +1119,7 @@ def main():
         print("bench: this device does not expose all 8 XCDs x 32 CUs - falling back to --engine chain", file=sys.stderr)
         args.engine = "chain"
     if args.engine == "chain":
-        out, y = bench_infer_chain(args, model, boxes, world, rank, dev, dist)
+        out, last = bench_infer_chain(args, model, boxes, world, rank, dev, dist)
     else:
         # DISTINCT clips in every step (up to 32 batches = one full launch; a longer run cycles through them): rank r owns
         # clips [r * nd * B, (r + 1) * nd * B) of the synthetic set
@@ -1090,13 +1127,16 @@ def main():
         all_np, _ = synth.make_batch(rank * nd * B, nd * B, T_FRAMES)
         all_dev = torch.from_numpy(all_np).to(dev)
         batches = [all_dev[i * B:(i + 1) * B] for i in range(nd)]
-        out, y = bench_infer_xcd(args, model, batches, world, rank, dev, dist)
+        out, last = bench_infer_xcd(args, model, batches, world, rank, dev, dist)
     # the ranks part here: everything below is rank 0's own (no collective), so that no rank waits in a process-group
     # shutdown while rank 0 is still measuring the extras
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()
     if rank == 0:
+        if args.dump_outputs:
+            # the last timed step's request: the last B clips of the last launch (xcd) / the step's own forward (chain)
+            dump_outputs(args.dump_outputs, {k: v[-B:] for k, v in last.items()})
         out.update(accuracy_block(dev))
         out.update(other_batches(model, boxes, dev))
         out.update(training_block(params, boxes, labels, dev))
@@ -1108,7 +1148,7 @@ def main():
         if world == 1 and not args.no_cpu_baseline:
             cb, y_cpu = cpu_baseline(boxes_np, params, args.cpu_seconds)
             out["cpu_baseline"] = cb
-            y_np = y.cpu().numpy()
+            y_np = last["y"].cpu().numpy()
             if args.engine == "chain":
                 # every timed step is the same B clips
                 err = max(float(np.abs(y_np[lo:lo + B] - y_cpu).max()) for lo in range(0, y_np.shape[0], B))
@@ -1326,7 +1366,7 @@ def bench_infer_xcd(args, model, batches, world, rank, dev, dist):
     model.use_xcd = "1"
     server = ReasonerServer(model, "opnet", max_clips=per_launch * B)
     exchange = dist is not None
-    state = {"y": None, "pred": None, "seen": 0, "gathered": []}
+    state = {"y": None, "logits": None, "pred_px": None, "seen": 0, "gathered": []}
     comm = torch.cuda.Stream(device=dev) if exchange else None
     # OPNET_DP_OVERLAP=1: the persistent launch does NOT wait for the previous launch's all-gather (see below) - the ordering was
     # chosen blind on one GPU; the switch lets the first multi-GPU run A/B it from two driver lines
@@ -1358,7 +1398,7 @@ def bench_infer_xcd(args, model, batches, world, rank, dev, dist):
                 gather_events.append((g0, g1, int(pred_px.numel()) * pred_px.element_size()))
             pred_px.record_stream(comm)
             state["gathered"] = (state["gathered"] + [gathered])[-4:]       # kept alive until the collectives are done
-        state["y"], state["pred"] = y, pred_px
+        state["y"], state["logits"], state["pred_px"] = y, server.last_output[1], pred_px
 
     def run(n):
         for i in range(n):
@@ -1448,7 +1488,7 @@ def bench_infer_xcd(args, model, batches, world, rank, dev, dist):
                                  "unit": "GB/s", "frac": round(model_bytes / kernel_s / 1e9 / HBM_PEAK_GBS, 4),
                                  "note": "SURVEY.md 8-d4 streaming-model bytes of the same clips (weights once per time step per "
                                          f"{B}-clip batch) over the kernel time; not bytes this kernel moves"}
-    return out, state["y"]
+    return out, {k: state[k] for k in ("y", "logits", "pred_px")}
 
 
 def bench_infer_chain(args, model, boxes, world, rank, dev, dist):
@@ -1484,14 +1524,14 @@ def bench_infer_chain(args, model, boxes, world, rank, dev, dist):
         k = i % S
         with torch.cuda.stream(streams[k]):
             with torch.no_grad():
-                y, _logits = model(boxes)
+                y, logits = model(boxes)
             pred_px, _, _ = metrics.postprocess_and_iou(y)
             if exchange:
                 local_acc[k][filled[k]].copy_(pred_px)
                 filled[k] += 1
         if exchange and filled[k] == G:
             flush(k)
-        return y, pred_px
+        return {"y": y, "logits": logits, "pred_px": pred_px}
 
     def drain():
         if exchange:
@@ -1540,13 +1580,12 @@ def bench_infer_chain(args, model, boxes, world, rank, dev, dist):
             if st is not main_stream:
                 st.wait_stream(main_stream)
         for i in range(args.steps):
-            last["y"], last["pred"] = step(i)
+            last.update(step(i))
         drain()
         ev1.record(main_stream)
 
     proof = collective_proof(dist, dev, world) if exchange else None
     elapsed, t_min, t_max, _all = timed_repeats(args, dev, dist, world, region)
-    y = last["y"]
     gpu_ms = ev0.elapsed_time(ev1)  # HIP events bracketing all launch streams of the last repeat: the kernels only
     # ONE launch's own duration: a single-stream pass (nothing overlaps it), HIP events on that stream
     single = streams[:1]
@@ -1585,7 +1624,7 @@ def bench_infer_chain(args, model, boxes, world, rank, dev, dist):
                                  "launches_in_flight": S, "amortised_launch_us": round(amort_us, 3),
                                  "note": "all algorithmic bytes of the timed region / GPU time with S forwards in flight: counts "
                                          "the weight stream once per concurrent forward; not a per-kernel figure"}
-    return out, y
+    return out, last
 
 
 if __name__ == "__main__":

@@ -12,6 +12,7 @@ regenerated from seeds by the tests).
 """
 from __future__ import annotations
 
+import ast
 import json
 import os
 import sys
@@ -23,7 +24,7 @@ import torch
 HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(HERE)
 REF = os.environ.get("OPNET_REFERENCE", "/root/reference")
-# OPNET_GOLDEN_OUT: write somewhere else (tests/test_golden_regeneration.py regenerates into a temp dir and compares)
+# OPNET_GOLDEN_OUT: write somewhere else (regenerate into a temp dir and diff against tests/golden/)
 OUT = os.environ.get("OPNET_GOLDEN_OUT") or os.path.join(REPO, "tests", "golden")
 
 sys.path.insert(0, REPO)
@@ -535,6 +536,55 @@ def gen_cone_ids():
     print("cone_ids:", len(cones), "cones of", n)
 
 
+def config_keys_read(path, names):
+    """string keys subscripted on (or read with .get) the variables `names` in the Python source file `path`"""
+    tree = ast.parse(open(path).read())
+    keys = set()
+    for node in ast.walk(tree):
+        if isinstance(node, ast.Subscript) and isinstance(node.value, ast.Name) and node.value.id in names:
+            sl = node.slice
+            if isinstance(sl, ast.Constant) and isinstance(sl.value, str):
+                keys.add(sl.value)
+        if isinstance(node, ast.Call) and isinstance(node.func, ast.Attribute) and node.func.attr == "get" and \
+                isinstance(node.func.value, ast.Name) and node.func.value.id in names and node.args and \
+                isinstance(node.args[0], ast.Constant) and isinstance(node.args[0].value, str):
+            keys.add(node.args[0].value)
+    return keys
+
+
+CONFIG_NAMES = {"config", "train_config", "inference_config", "preprocess_config"}
+MODEL_CONFIG_FILES = {"opnet": "opnet_model_config.json", "opnet_lstm_mlp": "opnet_lstm_mlp_model_config.json",
+                      "baseline_lstm": "baseline_lstm_model_config.json", "non_linear_lstm": "non_linear_lstm_model_config.json",
+                      "transformer_lstm": "transformer_lstm_model_config.json"}
+DRIVER_SOURCES = ["baselines/training_main.py", "baselines/inference_main.py", "baselines/cater_setup_inference.py",
+                  "baselines/preprocess_perception_main.py"]
+
+
+def gen_reference_configs(lm):
+    """tests/golden/reference_configs.json (tests/test_reference_configs.py): the reference's eight configs/*.json as they lie,
+    its supported-model lists (supported_models.py), the state_dict layout (names, shapes, dtypes in order) of each of its five
+    reasoner classes built from its own model config file, and the config keys each of its drivers reads (AST of the source)."""
+    sys.path.insert(0, REF)
+    from baselines import supported_models as rs
+    cdir = os.path.join(REF, "configs")
+    configs = {}
+    for name in sorted(os.listdir(cdir)):
+        with open(os.path.join(cdir, name)) as f:
+            configs[name] = json.load(f)
+    lists = {k: list(getattr(rs, k)) for k in ("PROGRAMMED_MODELS", "TRAINING_SUPPORTED_MODELS", "INFERENCE_SUPPORTED_MODELS",
+                                                 "TRAINING_SUPPORTED_MODELS_5_TRACKS", "TRAINING_SUPPORTED_MODELS_6_TRACKS",
+                                                 "DOUBLE_OUTPUT_MODELS", "NO_LABELS_MODELS")}
+    classes = {"opnet": lm.OPNet, "opnet_lstm_mlp": lm.OPNetLstmMlp, "baseline_lstm": lm.BaselineLstm,
+               "non_linear_lstm": lm.NonLinearLstm, "transformer_lstm": lm.TransformerLstm}
+    state_dicts = {base: [[k, list(v.shape), str(v.dtype)] for k, v in cls(dict(configs[MODEL_CONFIG_FILES[base]])).state_dict().items()]
+                   for base, cls in classes.items()}
+    keys = {src: sorted(config_keys_read(os.path.join(REF, src), CONFIG_NAMES)) for src in DRIVER_SOURCES}
+    with open(os.path.join(OUT, "reference_configs.json"), "w") as f:
+        json.dump({"configs": configs, "supported_models": lists, "state_dicts": state_dicts, "driver_config_keys": keys}, f, indent=1)
+        f.write("\n")
+    print("reference_configs:", len(configs), "files,", len(state_dicts), "classes")
+
+
 def main():
     """`python oracle/gen_golden.py` rewrites every fixture; `python oracle/gen_golden.py datasets cone_ids ...`
     only the named sections."""
@@ -566,6 +616,8 @@ def main():
         gen_datasets()
     if want("cone_ids"):
         gen_cone_ids()
+    if want("reference_configs"):
+        gen_reference_configs(lm)
     if want("no_labels"):
         gen_no_labels(lm)
     if want("grid_classes"):

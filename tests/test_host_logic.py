@@ -307,6 +307,34 @@ def test_bench_refuses_more_gpus_than_the_node_has():
     assert not any(l.startswith("{") for l in r.stdout.splitlines())
 
 
+def test_bench_dump_outputs_types_and_size_cap(tmp_path):
+    """bench.py --dump-outputs: floats as float32 (float64 kept), integers as float64; over 64 MB in all, every array keeps the
+    same seeded sample of its rows, and the kept row indices are written next to it"""
+    import bench
+    small = {"y": torch.arange(12, dtype=torch.float32).view(3, 4), "pred_px": torch.tensor([[1, -2]], dtype=torch.int32),
+             "loss": torch.tensor(0.5, dtype=torch.float64)}
+    bench.dump_outputs(str(tmp_path / "small"), small)
+    assert sorted(os.listdir(tmp_path / "small")) == ["loss.npy", "pred_px.npy", "y.npy"]
+    got = {n: np.load(tmp_path / "small" / f"{n}.npy") for n in small}
+    assert got["y"].dtype == np.float32 and np.array_equal(got["y"], small["y"].numpy())
+    assert got["pred_px"].dtype == np.float64 and np.array_equal(got["pred_px"], [[1, -2]])
+    assert got["loss"].dtype == np.float64 and got["loss"] == 0.5
+    # 80 MB of float32 rows + 8 MB of int64: each row holds its own index, so the sample is checkable
+    big = {"logits": torch.arange(5000, dtype=torch.float32).view(-1, 1).expand(5000, 4096),
+           "ids": torch.arange(1000, dtype=torch.int64).view(-1, 1).expand(1000, 1000)}
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), big)
+        files = sorted(os.listdir(tmp_path / d))
+        assert files == ["ids.npy", "ids.rows.npy", "logits.npy", "logits.rows.npy"]
+        assert sum(os.path.getsize(tmp_path / d / f) for f in files) <= 64 << 20
+    for name, n in (("logits", 5000), ("ids", 1000)):
+        rows = np.load(tmp_path / "a" / f"{name}.rows.npy")
+        vals = np.load(tmp_path / "a" / f"{name}.npy")
+        assert 0 < len(rows) < n and np.all(np.diff(rows) > 0) and np.array_equal(vals[:, 0], rows)
+        assert np.array_equal(rows, np.load(tmp_path / "b" / f"{name}.rows.npy"))
+        assert np.array_equal(vals, np.load(tmp_path / "b" / f"{name}.npy"))
+
+
 def test_reasoner_server_batches_requests_and_slices_outputs():
     """request batching (serving.ReasonerServer) with a stand-in model on CPU: several submitted minibatches run as ONE
     forward and every request gets exactly its own rows back"""
@@ -517,6 +545,9 @@ def test_small_batch_persistent_form_sizes_and_limits():
 
 # ---- data parallelism through the product entry points (parallel.init_from_env) --------------------
 
+NO_GPU = {"HIP_VISIBLE_DEVICES": "-1"}      # a child process started with this sees no GPU
+
+
 _ENTRY_RANK = r"""
 import json, os, sys
 import torch, torch.distributed as dist
@@ -542,8 +573,9 @@ def test_entry_points_join_the_job_torchrun_describes(tmp_path):
     port = str(33500 + os.getpid() % 1000)
     procs = []
     for r in range(2):
+        # the case under test is a host without a GPU: the ranks are kept from seeing one the machine may have
         env = dict(os.environ, WORLD_SIZE="2", RANK=str(r), LOCAL_RANK=str(r), MASTER_ADDR="127.0.0.1", MASTER_PORT=port,
-                   PYTHONPATH=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+                   PYTHONPATH=os.path.dirname(os.path.dirname(os.path.abspath(__file__))), **NO_GPU)
         env.pop("OPNET_FORCE_DIST", None)
         procs.append(subprocess.Popen([sys.executable, str(script), str(tmp_path)], env=env, stderr=subprocess.PIPE, text=True))
     for p in procs:
@@ -599,8 +631,10 @@ def _forced_world_of_one_worker(rank, world, port, tmp):
     open(os.path.join(tmp, "ok"), "w").write("ok")
 
 
-def test_forced_group_of_one_takes_the_data_parallel_branch(tmp_path):
+def test_forced_group_of_one_takes_the_data_parallel_branch(tmp_path, monkeypatch):
     import torch.multiprocessing as mp
+    for k, v in NO_GPU.items():          # a gloo group on the host: the spawned rank does not see a GPU the machine may have
+        monkeypatch.setenv(k, v)
     mp.spawn(_forced_world_of_one_worker, args=(1, 34500 + os.getpid() % 1000, str(tmp_path)), nprocs=1, join=True)
     assert os.path.exists(tmp_path / "ok")
 

@@ -1,5 +1,5 @@
 import cProfile, pstats, json, os, pickle, sys, tempfile, time
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from objectpermanence_amd.inference_main import reasoning_inference_main
 from synthdata import opnet as synth
