@@ -1,4 +1,5 @@
-"""Build-authored torch (CPU, autograd) restatement of the OPNet training step.
+"""Build-authored torch (autograd) restatement of the OPNet training step, on the host by default (`device=` takes any torch
+device: an fp64 step at full size is quick on the GPU).
 
 TEST INFRASTRUCTURE ONLY.  Used where the checker needs gradients: forward exactly as
 oracle/opnet_oracle.py (reference baselines/learned_models.py:35-52) but written with differentiable
@@ -78,12 +79,13 @@ def l1_mean(y: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
     return (y - labels).abs().mean()
 
 
-def loss_and_grads(boxes: np.ndarray, labels: np.ndarray, params: Dict[str, np.ndarray], dtype=torch.float32):
-    p = {k: torch.tensor(v, dtype=dtype, requires_grad=True) for k, v in params.items()}
-    y, _ = opnet_forward(torch.tensor(boxes, dtype=dtype), p)
-    loss = l1_mean(y, torch.tensor(labels, dtype=dtype))
+def loss_and_grads(boxes: np.ndarray, labels: np.ndarray, params: Dict[str, np.ndarray], dtype=torch.float32, device="cpu"):
+    """loss, {name: gradient}, y - host numpy arrays whatever `device` the step is evaluated on"""
+    p = {k: torch.tensor(v, dtype=dtype, device=device, requires_grad=True) for k, v in params.items()}
+    y, _ = opnet_forward(torch.tensor(boxes, dtype=dtype, device=device), p)
+    loss = l1_mean(y, torch.tensor(labels, dtype=dtype, device=device))
     loss.backward()
-    return float(loss.item()), {k: v.grad.numpy() for k, v in p.items()}, y.detach().numpy()
+    return float(loss.item()), {k: v.grad.cpu().numpy() for k, v in p.items()}, y.detach().cpu().numpy()
 
 
 def adam_step(params: Dict[str, np.ndarray], grads: Dict[str, np.ndarray], state: dict, lr=1e-3,
@@ -128,27 +130,39 @@ def opnet_lstm_mlp_forward(x: torch.Tensor, p: Dict[str, torch.Tensor]) -> torch
     return torch.relu(frames_boxes @ p["hidden_layer.weight"].t()) @ p["prediction_layer.weight"].t()
 
 
+def encoder_layer_forward(z: torch.Tensor, p: Dict[str, torch.Tensor], prefix: str, nhead: int) -> torch.Tensor:
+    """one post-LN nn.TransformerEncoderLayer without dropout (ReLU, dim_feedforward from linear1) over the S tokens of z [S, E];
+    parameters p[prefix + <state_dict name>]"""
+    E = z.shape[1]
+    z = encoder_attention_block(z, p, prefix, nhead)
+    f = torch.relu(z @ p[prefix + "linear1.weight"].t() + p[prefix + "linear1.bias"])
+    f = f @ p[prefix + "linear2.weight"].t() + p[prefix + "linear2.bias"]
+    return torch.nn.functional.layer_norm(z + f, (E,), p[prefix + "norm2.weight"], p[prefix + "norm2.bias"])
+
+
+def encoder_attention_block(z: torch.Tensor, p: Dict[str, torch.Tensor], prefix: str, nhead: int) -> torch.Tensor:
+    """the first half of encoder_layer_forward: norm1(z + self_attn(z)), the input of the feed-forward block"""
+    E = z.shape[1]
+    hd = E // nhead
+    qkv = z @ p[prefix + "self_attn.in_proj_weight"].t() + p[prefix + "self_attn.in_proj_bias"]
+    q, k, v = qkv[:, :E], qkv[:, E:2 * E], qkv[:, 2 * E:]
+    heads = []
+    for h in range(nhead):
+        sl = slice(h * hd, (h + 1) * hd)
+        heads.append(torch.softmax((q[:, sl] * hd ** -0.5) @ k[:, sl].t(), dim=-1) @ v[:, sl])
+    a = torch.cat(heads, dim=1) @ p[prefix + "self_attn.out_proj.weight"].t() + p[prefix + "self_attn.out_proj.bias"]
+    return torch.nn.functional.layer_norm(z + a, (E,), p[prefix + "norm1.weight"], p[prefix + "norm1.bias"])
+
+
 def transformer_lstm_forward(x: torch.Tensor, p: Dict[str, torch.Tensor], nhead: int) -> torch.Tensor:
     """TransformerLstm.forward (learned_models.py:175-197) without dropout, slot 0 only (the only slot that reaches
     the output; attention runs over the S = B*T tokens of the whole minibatch, as the reference's layout makes it)"""
     B, T = x.shape[:2]
     z = torch.relu(x[:, :, 0, :] @ p["boxes_linear.weight"].t()).reshape(B * T, -1)
     E = z.shape[1]
-    hd = E // nhead
     li = 0
     while f"attention_encoder.layers.{li}.linear1.weight" in p:
-        pre = f"attention_encoder.layers.{li}."
-        qkv = z @ p[pre + "self_attn.in_proj_weight"].t() + p[pre + "self_attn.in_proj_bias"]
-        q, k, v = qkv[:, :E], qkv[:, E:2 * E], qkv[:, 2 * E:]
-        heads = []
-        for h in range(nhead):
-            sl = slice(h * hd, (h + 1) * hd)
-            heads.append(torch.softmax((q[:, sl] * hd ** -0.5) @ k[:, sl].t(), dim=-1) @ v[:, sl])
-        a = torch.cat(heads, dim=1) @ p[pre + "self_attn.out_proj.weight"].t() + p[pre + "self_attn.out_proj.bias"]
-        z = torch.nn.functional.layer_norm(z + a, (E,), p[pre + "norm1.weight"], p[pre + "norm1.bias"])
-        f = torch.relu(z @ p[pre + "linear1.weight"].t() + p[pre + "linear1.bias"])
-        f = f @ p[pre + "linear2.weight"].t() + p[pre + "linear2.bias"]
-        z = torch.nn.functional.layer_norm(z + f, (E,), p[pre + "norm2.weight"], p[pre + "norm2.bias"])
+        z = encoder_layer_forward(z, p, f"attention_encoder.layers.{li}.", nhead)
         li += 1
     h = z.reshape(B, T, E)
     l = 0
@@ -159,13 +173,14 @@ def transformer_lstm_forward(x: torch.Tensor, p: Dict[str, torch.Tensor], nhead:
 
 
 def sibling_loss_and_grads(name: str, x: np.ndarray, labels: np.ndarray, params: Dict[str, np.ndarray], dtype=torch.float32,
-                           nhead: int = 2):
+                           nhead: int = 2, device="cpu"):
+    """loss, {name: gradient}, y - host numpy arrays whatever `device` the step is evaluated on"""
     fwd = {"baseline_lstm": baseline_lstm_forward, "non_linear_lstm": non_linear_lstm_forward,
            "opnet_lstm_mlp": opnet_lstm_mlp_forward,
            "transformer_lstm": lambda xx, pp: transformer_lstm_forward(xx, pp, nhead)}[name]
-    p = {k: torch.tensor(v, dtype=dtype, requires_grad=True) for k, v in params.items()}
-    y = fwd(torch.tensor(x, dtype=dtype), p)
-    loss = l1_mean(y, torch.tensor(labels, dtype=dtype))
+    p = {k: torch.tensor(v, dtype=dtype, device=device, requires_grad=True) for k, v in params.items()}
+    y = fwd(torch.tensor(x, dtype=dtype, device=device), p)
+    loss = l1_mean(y, torch.tensor(labels, dtype=dtype, device=device))
     loss.backward()
-    return float(loss.item()), {k: (v.grad.numpy() if v.grad is not None else np.zeros(v.shape, v.detach().numpy().dtype))
-                                for k, v in p.items()}, y.detach().numpy()
+    return float(loss.item()), {k: (v.grad.cpu().numpy() if v.grad is not None else np.zeros(v.shape, v.detach().cpu().numpy().dtype))
+                                for k, v in p.items()}, y.detach().cpu().numpy()
