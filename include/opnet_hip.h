@@ -246,6 +246,23 @@ int opnet_mlp_train_forward_f32(const float *boxes, const float *packed, float *
 int opnet_mlp_train_backward_f32(const float *dy, const float *packed, void *workspace, size_t workspace_bytes,
                                  float *g_ih1, float *g_hh1, float *g_sel, float *g_hidden_scratch, float *g_out,
                                  int B, int T, int H1, int H2, void *stream);
+
+/* ---- stateful streams: OPNet / OPNetLstmMlp with the LSTM state carried across calls ---------------------
+ * A call advances n streams by k >= 1 frames each.  A stream's state is a row of the caller-owned pool
+ *   state [capacity][opnet_stream_state_floats(H1, H2)] = [h1 | c1 | h2 | c2]   (torch nn.LSTM unit order)
+ * named by slots[i] (device int32, n of them).  The CALLER checks that each slot is in [0, capacity) and appears at
+ * most once per call (the kernels skip a slot outside the pool; a repeated slot is a race).  A zero row is the
+ * reference's zero initial state.  boxes [n][k][90], y [n][k][4], logits [n][15][k] as opnet_forward_f32; packed is
+ * the image of opnet_pack_weights_f32 (mlp = 0, OPNet) or opnet_mlp_pack_weights_f32 (mlp = 1, OPNetLstmMlp, whose
+ * h2 / c2 columns are left untouched).  The rows named are read before and written after the k frames; the others
+ * are not touched.  k + 5 dependent launches, each frame with the arithmetic of the launch chain (opnet_forward_f32
+ * of the same n clips): any chunking of a clip's frames gives the same bits as that whole-clip forward. */
+size_t opnet_stream_state_floats(int H1, int H2);                   /* 2*H1 + 2*H2; 0 on bad sizes */
+size_t opnet_stream_workspace_bytes(int n, int k, int H1, int H2);   /* 0 on bad sizes */
+int opnet_stream_step_f32(const float *boxes, const int32_t *slots, float *state, const float *packed, float *y,
+                          float *logits, void *workspace, size_t workspace_bytes, int n, int k, int capacity, int H1,
+                          int H2, int mlp, void *stream);
+
 /* L (1..3) stacked bias-free LSTM layers (input width KX, hidden H each) + Linear H->4:
  *   x [B,T,KX] -> y [B,T,4].  BaselineLstm (:92-118): L=1, KX=75.  NonLinearLstm (:121-151): L=2,
  *   KX=15*F after opseq_slot_embed_relu_f32.  TransformerLstm's LSTM half (:170-172,192-195): L=2, KX=E.

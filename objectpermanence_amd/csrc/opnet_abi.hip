@@ -14,6 +14,7 @@
 #include "attn_kernels.hip"
 #include "enc_train_kernels.hip"
 #include "attn_train_kernels.hip"
+#include "opnet_stream_kernels.hip"
 
 #include <stdarg.h>
 #include <stdlib.h>
@@ -3005,6 +3006,7 @@ extern "C" int opseq_encoder_layer_batched_f32(float *z, const float *in_w, cons
 }
 
 #include "enc_train_abi.hip"
+#include "opnet_stream_abi.hip"
 
 // ------------------------------------------------------------------------------------------------
 // detector backbone primitives (NHWC fp32)

@@ -1,0 +1,66 @@
+// opnet_stream_abi.hip - host side of the stateful OPNet streams (C ABI: opnet_stream_*; kernels in opnet_stream_kernels.hip).
+// Included by opnet_abi.hip (one translation unit: it uses that file's fail / HIP_TRY / check_dims / aligned16 and the launch
+// chain's step_kernel / step_grid / step_threads).
+#pragma once
+
+extern "C" size_t opnet_stream_state_floats(int H1, int H2)
+{
+    if (check_dims(1, 1, H1, H2)) return 0;
+    return 2 * (size_t)H1 + 2 * (size_t)H2;
+}
+
+// the chain's inference workspace for n clips x k frames (its OpnetIO head stays unused: the boundary kernels take their
+// arguments by value)
+extern "C" size_t opnet_stream_workspace_bytes(int n, int k, int H1, int H2)
+{
+    if (check_dims(n, k, H1, H2)) return 0;
+    if ((n + 31) / 32 > 65535) { fail(OPNET_ESHAPE, "n=%d streams exceed one call's 65535 row blocks", n); return 0; }
+    return workspace_layout(n, k, H1, H2).total;
+}
+
+// prologue -> k + 3 step launches -> write-back: k + 5 dependent launches on `stream`, no host synchronisation
+extern "C" int opnet_stream_step_f32(const float *boxes, const int32_t *slots, float *state, const float *packed, float *y,
+                                     float *logits, void *workspace, size_t workspace_bytes, int n, int k, int capacity, int H1,
+                                     int H2, int mlp, void *stream)
+{
+    if (int rc = check_dims(n, k, H1, H2)) return rc;
+    if (capacity <= 0) return fail(OPNET_ESHAPE, "capacity=%d must be positive", capacity);
+    if ((n + 31) / 32 > 65535) return fail(OPNET_ESHAPE, "n=%d streams exceed one call's 65535 row blocks", n);
+    if (mlp != 0 && mlp != 1) return fail(OPNET_EINVAL, "mlp must be 0 or 1 (got %d)", mlp);
+    if (!boxes || !slots || !state || !packed || !y || !logits || !workspace) return fail(OPNET_EINVAL, "null pointer");
+    if (!aligned16(state) || !aligned16(packed) || !aligned16(y) || !aligned16(workspace) || (((uintptr_t)boxes) & 7u) ||
+        (((uintptr_t)slots) & 3u) || (((uintptr_t)logits) & 3u))
+        return fail(OPNET_EINVAL, "state/packed/y/workspace must be 16-byte, boxes 8-byte and slots/logits 4-byte aligned");
+    const WorkspaceLayout W = workspace_layout(n, k, H1, H2);
+    if (workspace_bytes < W.total) return fail(OPNET_EWORKSPACE, "workspace %zu B < %zu B", workspace_bytes, W.total);
+
+    StreamArgs s;
+    memset(&s, 0, sizeof(s));
+    step_args_inference(&s.a, (char *)workspace, packed, n, k, H1, H2);
+    s.a.mlp = mlp;
+    s.boxes = boxes;
+    s.slots = slots;
+    s.state = state;
+    s.y = y;
+    s.logits = logits;
+    s.xp = (float4 *)((char *)workspace + W.xp);
+    s.capacity = capacity;
+    const StepArgs &a = s.a;
+    hipStream_t st = (hipStream_t)stream;
+
+    // gather workgroups per row block: one work item per (unit quad, clip), up to 256 a thread
+    const int gather_items = (H1 + H2) / 4 * 32;
+    const int G = (gather_items + 255) / 256 < 64 ? (gather_items + 255) / 256 : 64;
+    opnet_stream_prologue<<<dim3(k + G, a.RB), 256, 0, st>>>(s);
+    // the chain's step kernel for this shape; the kernarg-preload form (opnet_step_pl) is left out: it carves its buffers
+    // from the chain's own workspace, and computes the same body as opnet_step<4, 8>
+    const opnet_step_fn stepk = step_kernel(a);
+    const dim3 grid = step_grid(a);
+    for (int t = 0; t < k + 3; ++t) stepk<<<grid, step_threads(a), 0, st>>>(a, t);
+    const long items = (long)a.B * OPNET_SLOTS * k > (long)a.RB * 32 * (H1 + H2) / 4 ? (long)a.B * OPNET_SLOTS * k
+                                                                                     : (long)a.RB * 32 * (H1 + H2) / 4;
+    const unsigned wb = (unsigned)((items + 255) / 256 > 1024 ? 1024 : (items + 255) / 256);
+    opnet_stream_writeback<<<wb, 256, 0, st>>>(s);
+    HIP_TRY(hipGetLastError());
+    return OPNET_OK;
+}

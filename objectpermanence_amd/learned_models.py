@@ -1228,13 +1228,34 @@ class OPNetLstmMlp(AbstractCaterModel):
         self._packed, self._key, self._ws = None, None, {}
         self._tpacked, self._tscratch, self._tws, self._tws_key, self._train_gen = None, None, None, None, 0
 
+    def _weights(self):
+        return [self.object_to_track_LSTM.weight_ih_l0, self.object_to_track_LSTM.weight_hh_l0,
+                self.object_to_track_prediction.weight, self.hidden_layer.weight, self.prediction_layer.weight]
+
+    def _packed_weights(self, device: torch.device) -> torch.Tensor:
+        """the packed inference image (opnet_mlp_pack_weights_f32), re-packed on the current stream whenever a weight
+        changed since the last pack"""
+        lib = _lib.load()
+        ws_list = self._weights()
+        key = _weights_key(ws_list, device)
+        if self._key != key:
+            nbytes = lib.opnet_packed_weights_bytes(self._h1, self._h2)
+            if nbytes == 0:
+                _lib.check(-2, "opnet_packed_weights_bytes")
+            if self._packed is None or self._packed.device != device:
+                self._packed = torch.zeros(nbytes // 4, dtype=torch.float32, device=device)
+            rc = lib.opnet_mlp_pack_weights_f32(*(w.data_ptr() for w in ws_list), self._packed.data_ptr(), nbytes,
+                                                self._h1, self._h2, _stream_ptr(device))
+            _lib.check(rc, "opnet_mlp_pack_weights_f32")
+            self._key = key
+        return self._packed
+
     def forward(self, boxes: torch.Tensor):
         _check_input(self, boxes, 6)
         lib = _lib.load()
         boxes = boxes.contiguous().float()
         B, T, dev = int(boxes.shape[0]), int(boxes.shape[1]), boxes.device
-        ws_list = [self.object_to_track_LSTM.weight_ih_l0, self.object_to_track_LSTM.weight_hh_l0,
-                   self.object_to_track_prediction.weight, self.hidden_layer.weight, self.prediction_layer.weight]
+        ws_list = self._weights()
         if _wants_grad(self):
             for w in ws_list:
                 if w.device != dev or w.dtype != torch.float32 or not w.is_contiguous():
@@ -1242,17 +1263,7 @@ class OPNetLstmMlp(AbstractCaterModel):
             return _OPNetMlpTrainFunction.apply(self, boxes, *ws_list)
         with torch.cuda.device(dev):
             stream = _stream_ptr(dev)
-            key = _weights_key(ws_list, dev)
-            if self._key != key:
-                nbytes = lib.opnet_packed_weights_bytes(self._h1, self._h2)
-                if nbytes == 0:
-                    _lib.check(-2, "opnet_packed_weights_bytes")
-                if self._packed is None or self._packed.device != dev:
-                    self._packed = torch.zeros(nbytes // 4, dtype=torch.float32, device=dev)
-                rc = lib.opnet_mlp_pack_weights_f32(*(w.data_ptr() for w in ws_list), self._packed.data_ptr(), nbytes,
-                                                    self._h1, self._h2, stream)
-                _lib.check(rc, "opnet_mlp_pack_weights_f32")
-                self._key = key
+            self._packed_weights(dev)
             wkey = (B, T, str(dev), stream)
             if wkey not in self._ws:
                 self._ws = {wkey: torch.empty(lib.opnet_workspace_bytes(B, T, self._h1, self._h2), dtype=torch.uint8, device=dev)}

@@ -1,0 +1,205 @@
+"""Stateful OPNet streams: frames that arrive over time, with the LSTM state carried across calls.
+
+`OPNet.forward` is whole-clip: every call starts from h0 = c0 = 0 (reference learned_models.py:39,46).  OPNet and
+OPNetLstmMlp are causal, so a clip cut into chunks whose state is carried from one chunk to the next computes the same
+function.  `OPNetStreams` keeps that state in a pool on the device, one row per open stream, and advances any set of
+streams by k frames in one call (opnet_stream_step_f32, include/opnet_hip.h): k + 5 launches of the launch chain's own
+kernels, so any chunking of a clip gives the bits of the whole-clip launch-chain forward of the same number of clips.
+
+    streams = OPNetStreams(model, capacity=1024)
+    ids = streams.open(3)                          # zero state
+    y, logits = streams.step(ids, boxes)           # boxes [n, k, 15, 6] -> y [n, k, 4], logits [n, 15, k]
+    h1, c1, h2, c2 = streams.get_state(ids)        # [1, n, H] each (nn.LSTM's h_n / c_n); OPNetLstmMlp: h2 = c2 = None
+    streams.set_state(ids, h1, c1, h2, c2)
+    streams.close(ids)
+"""
+from __future__ import annotations
+
+from typing import Dict, List, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import _lib
+from .learned_models import OPNet, OPNetLstmMlp, _stream_ptr
+
+
+class StreamSlots:
+    """Host bookkeeping of a pool's slot ids: which are open, and the checks every call makes before it launches
+    anything (ids in range, distinct within the call, open)."""
+
+    def __init__(self, capacity: int):
+        capacity = int(capacity)
+        if capacity <= 0:
+            raise ValueError(f"capacity must be positive, got {capacity}")
+        self.capacity = capacity
+        self._is_open = np.zeros(capacity, dtype=bool)
+
+    @property
+    def free(self) -> int:
+        return int(self.capacity - self._is_open.sum())
+
+    def open(self, count: int) -> np.ndarray:
+        """the `count` lowest free ids, now open"""
+        count = int(count)
+        if count <= 0:
+            raise ValueError(f"count must be positive, got {count}")
+        free = np.flatnonzero(~self._is_open)
+        if count > len(free):
+            raise RuntimeError(f"stream pool is full: {count} requested, {len(free)} of {self.capacity} free")
+        ids = free[:count]
+        self._is_open[ids] = True
+        return ids
+
+    def close(self, ids) -> None:
+        self._is_open[self.check(ids)] = False
+
+    def check(self, ids) -> np.ndarray:
+        """ids as an int64 array, or an exception: out of range, repeated, or not open"""
+        idx = np.asarray([ids] if isinstance(ids, (int, np.integer)) else ids)
+        if idx.ndim != 1 or idx.size == 0:
+            raise ValueError("ids must be a non-empty list of slot ids")
+        if idx.dtype.kind not in "iu":
+            raise TypeError(f"slot ids must be integers, got {idx.dtype}")
+        idx = idx.astype(np.int64)
+        bad = idx[(idx < 0) | (idx >= self.capacity)]
+        if bad.size:
+            raise IndexError(f"slot id {int(bad[0])} out of range [0, {self.capacity})")
+        if np.unique(idx).size != idx.size:
+            raise ValueError("slot ids must be distinct within one call")
+        closed = idx[~self._is_open[idx]]
+        if closed.size:
+            raise KeyError(f"stream {int(closed[0])} is not open")
+        return idx
+
+
+class OPNetStreams:
+    """A pool of `capacity` OPNet (or OPNetLstmMlp) streams on the model's ROCm device.  Calls are enqueued on the
+    current torch stream and are inference only (no autograd graph).  The model's own packed weight image is used, so an
+    in-place parameter update takes effect on the next call."""
+
+    MAX_WORKSPACES = 8       # (n, k, stream) workspaces kept alive, least recently used dropped first
+
+    def __init__(self, model, capacity: int = 1024):
+        if isinstance(model, OPNet):
+            self._mlp = 0
+        elif isinstance(model, OPNetLstmMlp):
+            self._mlp = 1
+        else:
+            raise TypeError(f"OPNetStreams serves OPNet and OPNetLstmMlp, not {type(model).__name__} (the other reasoners "
+                            "are not streamed: transformer_lstm's encoder attends over the whole sequence)")
+        slots = StreamSlots(capacity)
+        dev = next(model.parameters()).device
+        if dev.type != "cuda":
+            raise RuntimeError("OPNetStreams runs on MI355X only: move the model to a ROCm device first; there is no CPU "
+                               "fallback")
+        lib = _lib.load()
+        self.model = model
+        self.device = dev
+        self.slots = slots
+        self.capacity = slots.capacity
+        self.H1, self.H2 = model._h1, model._h2
+        self._row = int(lib.opnet_stream_state_floats(self.H1, self.H2))
+        if self._row == 0:
+            _lib.check(-2, "opnet_stream_state_floats")
+        self.state = torch.zeros((self.capacity, self._row), dtype=torch.float32, device=dev)
+        self._ws: Dict[Tuple[int, int, int], torch.Tensor] = {}
+
+    # -- slots --------------------------------------------------------------------------------
+    @property
+    def free(self) -> int:
+        return self.slots.free
+
+    def open(self, count: int = 1) -> List[int]:
+        """`count` new streams with a zero state (the reference's h0 = c0 = 0); returns their slot ids"""
+        ids = self.slots.open(count)
+        with torch.cuda.device(self.device):
+            self.state.index_fill_(0, torch.from_numpy(ids).to(self.device), 0.0)
+        return [int(i) for i in ids]
+
+    def close(self, ids: Sequence[int]) -> None:
+        self.slots.close(ids)
+
+    # -- state --------------------------------------------------------------------------------
+    def get_state(self, ids: Sequence[int]):
+        """(h1, c1, h2, c2) of the streams, [1, n, H] each in nn.LSTM's (num_layers, batch, hidden) layout; copies"""
+        idx = self.slots.check(ids)
+        H1, H2 = self.H1, self.H2
+        with torch.cuda.device(self.device):
+            rows = self.state.index_select(0, torch.from_numpy(idx).to(self.device))
+        h1 = rows[:, :H1].unsqueeze(0).contiguous()
+        c1 = rows[:, H1:2 * H1].unsqueeze(0).contiguous()
+        if self._mlp:
+            return h1, c1, None, None
+        h2 = rows[:, 2 * H1:2 * H1 + H2].unsqueeze(0).contiguous()
+        c2 = rows[:, 2 * H1 + H2:].unsqueeze(0).contiguous()
+        return h1, c1, h2, c2
+
+    def set_state(self, ids: Sequence[int], h1: torch.Tensor, c1: torch.Tensor,
+                  h2: Optional[torch.Tensor] = None, c2: Optional[torch.Tensor] = None) -> None:
+        """overwrite the state of open streams with [1, n, H] tensors (h2 / c2 are required for OPNet and must be None
+        for OPNetLstmMlp, which has no video LSTM)"""
+        idx = self.slots.check(ids)
+        n = idx.size
+        parts = [(h1, self.H1, "h1"), (c1, self.H1, "c1")]
+        if self._mlp:
+            if h2 is not None or c2 is not None:
+                raise ValueError("OPNetLstmMlp has no video LSTM: h2 and c2 must be None")
+        else:
+            if h2 is None or c2 is None:
+                raise ValueError("OPNet needs h2 and c2")
+            parts += [(h2, self.H2, "h2"), (c2, self.H2, "c2")]
+        cols = []
+        for t, H, name in parts:
+            if tuple(t.shape) != (1, n, H):
+                raise ValueError(f"{name} must be [1, {n}, {H}], got {tuple(t.shape)}")
+            cols.append(t[0].to(device=self.device, dtype=torch.float32))
+        with torch.cuda.device(self.device):
+            dst = torch.from_numpy(idx).to(self.device)
+            if self._mlp:      # leave the h2 / c2 columns as they are
+                self.state[:, :2 * self.H1].index_copy_(0, dst, torch.cat(cols, dim=1))
+            else:
+                self.state.index_copy_(0, dst, torch.cat(cols, dim=1))
+
+    # -- frames -------------------------------------------------------------------------------
+    def step(self, ids: Sequence[int], boxes: torch.Tensor):
+        """advance the streams `ids` by k frames: boxes [n, k, 15, 6] (row i belongs to ids[i]) -> (y [n, k, 4],
+        logits [n, 15, k]), the outputs of those frames"""
+        if not isinstance(boxes, torch.Tensor) or not boxes.is_cuda:
+            raise RuntimeError("OPNetStreams.step runs on MI355X only: `boxes` must be a tensor on a ROCm device")
+        if boxes.device != self.device:
+            raise ValueError(f"boxes are on {boxes.device}, the stream pool on {self.device}")
+        idx = self.slots.check(ids)
+        n = idx.size
+        if boxes.dim() != 4 or boxes.shape[0] != n or boxes.shape[2] != 15 or boxes.shape[3] != 6 or boxes.shape[1] < 1:
+            raise ValueError(f"boxes must be [n={n}, k>=1, 15, 6], got {tuple(boxes.shape)}")
+        k = int(boxes.shape[1])
+        lib = _lib.load()
+        with torch.no_grad(), torch.cuda.device(self.device):
+            boxes = boxes.contiguous().float()
+            packed = self.model._packed_weights(self.device)
+            stream = _stream_ptr(self.device)
+            ws = self._workspace(n, k, stream)
+            slots = torch.from_numpy(idx.astype(np.int32)).to(self.device)      # one small H2D copy on this stream
+            y = torch.empty((n, k, 4), dtype=torch.float32, device=self.device)
+            logits = torch.empty((n, 15, k), dtype=torch.float32, device=self.device)
+            rc = lib.opnet_stream_step_f32(boxes.data_ptr(), slots.data_ptr(), self.state.data_ptr(), packed.data_ptr(),
+                                           y.data_ptr(), logits.data_ptr(), ws.data_ptr(), ws.numel(), n, k, self.capacity,
+                                           self.H1, self.H2, self._mlp, stream)
+            _lib.check(rc, "opnet_stream_step_f32")
+        return y, logits
+
+    def _workspace(self, n: int, k: int, stream: int) -> torch.Tensor:
+        # one per (n, k, stream): calls on different streams must not share one.  A dropped workspace may still be read
+        # by launches on its stream; the caching allocator only hands the block back to that stream, behind them.
+        key = (n, k, stream)
+        ws = self._ws.pop(key, None)
+        if ws is None:
+            nbytes = _lib.load().opnet_stream_workspace_bytes(n, k, self.H1, self.H2)
+            if nbytes == 0:
+                _lib.check(-2, "opnet_stream_workspace_bytes")
+            while len(self._ws) >= self.MAX_WORKSPACES:
+                self._ws.pop(next(iter(self._ws)))
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        self._ws[key] = ws          # most recently used at the end
+        return ws
