@@ -278,6 +278,29 @@ int opseq_lstm_stack_forward_f32(const float *x, const float *packed, float *y, 
  * the library (host-side objects; opseq_graph_cache_clear() releases them). Bit-identical results. */
 int opseq_lstm_stack_forward_graph_f32(const float *x, const float *packed, float *y, void *workspace,
                                        size_t workspace_bytes, int B, int T, int L, int KX, int H, void *stream);
+
+/* ---- stateful streams of the stack: BaselineLstm / NonLinearLstm with the LSTM state carried across calls ---------------
+ * A call advances n streams by k >= 1 frames each.  A stream's state is a row of the caller-owned pool
+ *   state [capacity][opseq_stream_state_floats(L, H)] = [h_0 | c_0 | h_1 | c_1 ...]   (torch nn.LSTM unit order, per layer)
+ * named by slots[i] (device int32, n of them).  The CALLER checks that each slot is in [0, capacity) and appears at most
+ * once per call (the kernels skip a slot outside the pool; a repeated slot is a race).  A zero row is the reference's zero
+ * initial state.  x [n][k][KX] and y [n][k][4] as opseq_lstm_stack_forward_f32 (x 16-byte aligned when layer 0's input is
+ * hoisted: KX % 16 == 0 and KX >= 2H); packed is the image of opseq_lstm_stack_pack_weights_f32.  The rows named are read
+ * before and written after the k frames; the others are not touched.  Each frame has the arithmetic of the launch chain
+ * (opseq_lstm_stack_forward_f32 of the same n clips): any chunking of a clip's frames gives the same bits as that
+ * whole-clip forward.  k + 2L + 1 dependent launches, plus the hoisted input product: a kernel for few rows when the
+ * k * ceil(n/16) * 16 rows it computes are <= OPSEQ_STREAM_SKINNY_MAX_ROWS (environment, read per call; 0 = never), else
+ * the tiled GEMM and its repack - the same bits either way.  The workspace is the chain's for n clips x k frames. */
+size_t opseq_stream_state_floats(int L, int H);                                 /* 2 * L * H; 0 on bad sizes */
+size_t opseq_stream_workspace_bytes(int n, int k, int L, int KX, int H);        /* 0 on bad sizes */
+int opseq_stream_step_f32(const float *x, const int32_t *slots, float *state, const float *packed, float *y, void *workspace,
+                          size_t workspace_bytes, int n, int k, int capacity, int L, int KX, int H, void *stream);
+/* the hoisted layer-0 input product of such a call alone (NonLinearLstm; for measurement and tests):
+ * xg [k][ceil(n/32)][H][32][4] = x . W_ih0^T in the step kernel's layout, clips past n zero.  route 0 = as
+ * opseq_stream_step_f32 picks it (the skinny kernel computes k * ceil(n/16) * 16 rows; it takes calls of at most
+ * OPSEQ_STREAM_SKINNY_MAX_ROWS of them), 1 = the skinny kernel, 2 = the tiled GEMM + repack.  Same bits either way. */
+int opseq_stream_input_product_f32(const float *x, const float *packed, float *xg, void *workspace, size_t workspace_bytes,
+                                   int n, int k, int L, int KX, int H, int route, void *stream);
 /* ---- the same stack as ONE persistent launch (csrc/seq_xcd_kernels.hip) --------------------------------------------------
  * Replaces the T + 2L - 1 step launches above for the reference's three stacked reasoners (learned_models.py:99-101,
  * 135-137, 170-171: H = 512; L = 1 with KX = 75, L = 2 with KX = 256 or the hoisted KX = 3840) on a whole MI355X

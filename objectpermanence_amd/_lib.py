@@ -134,6 +134,16 @@ def _declare(lib):
     lib.opseq_lstm_stack_forward_f32.argtypes = [fp, fp, fp, c_void_p, c_size_t, c_int, c_int, c_int, c_int, c_int, c_void_p]
     lib.opseq_lstm_stack_forward_graph_f32.restype = c_int
     lib.opseq_lstm_stack_forward_graph_f32.argtypes = lib.opseq_lstm_stack_forward_f32.argtypes
+    lib.opseq_stream_state_floats.restype = c_size_t
+    lib.opseq_stream_state_floats.argtypes = [c_int, c_int]
+    lib.opseq_stream_workspace_bytes.restype = c_size_t
+    lib.opseq_stream_workspace_bytes.argtypes = [c_int, c_int, c_int, c_int, c_int]
+    lib.opseq_stream_step_f32.restype = c_int
+    lib.opseq_stream_step_f32.argtypes = [fp, fp, fp, fp, fp, c_void_p, c_size_t, c_int, c_int, c_int, c_int, c_int, c_int,
+                                          c_void_p]
+    lib.opseq_stream_input_product_f32.restype = c_int
+    lib.opseq_stream_input_product_f32.argtypes = [fp, fp, fp, c_void_p, c_size_t, c_int, c_int, c_int, c_int, c_int, c_int,
+                                                   c_void_p]
     lib.opseq_xcd_supported.restype = c_int
     lib.opseq_xcd_supported.argtypes = [c_int, c_int, c_int]
     lib.opseq_xcd_enable.restype = None
@@ -313,6 +323,7 @@ EXPORTS = [
     "opnet_mlp_train_pack_weights_f32", "opnet_mlp_train_forward_f32", "opnet_mlp_train_backward_f32",
     "opseq_lstm_stack_packed_bytes", "opseq_lstm_stack_workspace_bytes", "opseq_lstm_stack_pack_weights_f32",
     "opseq_lstm_stack_forward_f32", "opseq_lstm_stack_forward_graph_f32", "opseq_graph_cache_clear",
+    "opseq_stream_state_floats", "opseq_stream_workspace_bytes", "opseq_stream_step_f32", "opseq_stream_input_product_f32",
     "opseq_xcd_supported", "opseq_xcd_enable", "opseq_xcd_max_batch", "opseq_xcd_packed_bytes", "opseq_xcd_workspace_bytes",
     "opseq_xcd_status_offset", "opseq_xcd_pack_weights_f32", "opseq_xcd_forward_f32", "opseq_lstm_stack_train_status_offset", "opseq_xcd_set_trace",
     "opseq_xcdt_supported", "opseq_xcdt_enable", "opseq_xcdt_max_batch", "opseq_xcdt_packed_bytes", "opseq_xcdt_workspace_bytes",

@@ -15,6 +15,7 @@
 #include "enc_train_kernels.hip"
 #include "attn_train_kernels.hip"
 #include "opnet_stream_kernels.hip"
+#include "seq_stream_kernels.hip"
 
 #include <stdarg.h>
 #include <stdlib.h>
@@ -1867,19 +1868,15 @@ extern "C" void opseq_graph_cache_clear(void)
     g_stack_graphs.clear();
 }
 
-static int stack_forward_impl(const float *x, const float *packed, float *y, void *workspace,
-                              size_t workspace_bytes, int B, int T, int L, int KX, int H, void *stream, bool graph)
+// The step kernel's arguments for an inference forward of B clips x T frames over `workspace` (the chain's and the streams'
+// layout, stack_workspace_layout); returns the step launches' grid.  With a hoisted layer-0 input the steps read xg (W.xg),
+// which the caller fills first (stack_hoisted_input_tiled or the streams' skinny product).
+static dim3 stack_args_inference(StackArgs *ap, char *w, const float *packed, int B, int T, int L, int KX, int H)
 {
-    if (int rc = check_stack(B, T, L, KX, H)) return rc;
-    if (!x || !packed || !y || !workspace) return fail(OPNET_EINVAL, "null pointer");
-    if (!aligned16(packed) || !aligned16(y) || !aligned16(workspace))
-        return fail(OPNET_EINVAL, "packed/y/workspace must be 16-byte aligned");
     const StackWorkspaceLayout W = stack_workspace_layout(B, T, L, KX, H);
-    if (workspace_bytes < W.total) return fail(OPNET_EWORKSPACE, "workspace %zu B < %zu B", workspace_bytes, W.total);
     const StackPackedLayout P = stack_packed_layout(L, KX, H);
-    char *w = (char *)workspace;
     const int RB = (B + 31) / 32;
-    StackArgs a;
+    StackArgs &a = *ap;
     memset(&a, 0, sizeof(a));
     a.B = B; a.T = T; a.RB = RB; a.L = L;
     a.xp = (const float4 *)(w + W.xp);
@@ -1898,31 +1895,59 @@ static int stack_forward_impl(const float *x, const float *packed, float *y, voi
             ntiles += H / 4;
         }
     }
-    const int nlaunch = T + 2 * L - 1;
-    a.headA = (const float4 *)(packed + P.head);
-    a.ystage = (float4 *)(w + W.ystage);
-    hipStream_t st = (hipStream_t)stream;
     if (stack_hoists_input(KX, H)) {
-        if (!aligned16(x)) return fail(OPNET_EINVAL, "x must be 16-byte aligned");
-        // G [B*T][4H] = x [B*T][KX] . W_ih0^T  (a 1x1 "conv" over B*T pixels), then into the step kernel's layout
-        ConvArgs c = {};
-        c.X = x; c.Wt = packed + P.wih0g; c.bias = nullptr; c.R = nullptr; c.Y = (float *)(w + W.gemm);
-        c.N = 1; c.H = 1; c.W = B * T; c.Cin = KX; c.Cout = 4 * H; c.KH = 1; c.KW = 1; c.stride = 1; c.pad = 0;
-        c.OH = 1; c.OW = B * T; c.KP = KX; c.relu = 0;
-        launch_conv_tiled(c, (long)B * T, st);
-        const long nx = (long)T * RB * 32 * H;
-        stack_xg_repack<<<(unsigned)((nx + 255) / 256 > 8192 ? 8192 : (nx + 255) / 256), 256, 0, st>>>(
-            (const float4 *)(w + W.gemm), (float4 *)(w + W.xg), B, T, RB, H);
         a.layer[0].xg = (float4 *)(w + W.xg);
         a.layer[0].a_skip = P.nhx[0];
         a.layer[0].nhx = 0;
+    }
+    a.headA = (const float4 *)(packed + P.head);
+    a.ystage = (float4 *)(w + W.ystage);
+    return dim3((ntiles + 7) / 8 * 8, RB < OPNET_MAX_GY ? RB : OPNET_MAX_GY, 1);   // XCD-aligned, see step_grid
+}
+
+// the hoisted layer-0 input product through the tiled GEMM: G [B*T][4H] = x [B*T][KX] . W_ih0^T (a 1x1 "conv" over B*T
+// pixels, into the workspace w), then into the step kernel's layout xg [T][RB][H][32]
+static void stack_hoisted_input_tiled(const float *x, const float *packed, char *w, float4 *xg, int B, int T, int L, int KX,
+                                      int H, hipStream_t st)
+{
+    const StackWorkspaceLayout W = stack_workspace_layout(B, T, L, KX, H);
+    const StackPackedLayout P = stack_packed_layout(L, KX, H);
+    const int RB = (B + 31) / 32;
+    ConvArgs c = {};
+    c.X = x; c.Wt = packed + P.wih0g; c.bias = nullptr; c.R = nullptr; c.Y = (float *)(w + W.gemm);
+    c.N = 1; c.H = 1; c.W = B * T; c.Cin = KX; c.Cout = 4 * H; c.KH = 1; c.KW = 1; c.stride = 1; c.pad = 0;
+    c.OH = 1; c.OW = B * T; c.KP = KX; c.relu = 0;
+    launch_conv_tiled(c, (long)B * T, st);
+    const long nx = (long)T * RB * 32 * H;
+    stack_xg_repack<<<(unsigned)((nx + 255) / 256 > 8192 ? 8192 : (nx + 255) / 256), 256, 0, st>>>(
+        (const float4 *)(w + W.gemm), xg, B, T, RB, H);
+}
+
+static int stack_forward_impl(const float *x, const float *packed, float *y, void *workspace,
+                              size_t workspace_bytes, int B, int T, int L, int KX, int H, void *stream, bool graph)
+{
+    if (int rc = check_stack(B, T, L, KX, H)) return rc;
+    if (!x || !packed || !y || !workspace) return fail(OPNET_EINVAL, "null pointer");
+    if (!aligned16(packed) || !aligned16(y) || !aligned16(workspace))
+        return fail(OPNET_EINVAL, "packed/y/workspace must be 16-byte aligned");
+    const StackWorkspaceLayout W = stack_workspace_layout(B, T, L, KX, H);
+    if (workspace_bytes < W.total) return fail(OPNET_EWORKSPACE, "workspace %zu B < %zu B", workspace_bytes, W.total);
+    const StackPackedLayout P = stack_packed_layout(L, KX, H);
+    char *w = (char *)workspace;
+    const int RB = (B + 31) / 32;
+    StackArgs a;
+    const dim3 grid = stack_args_inference(&a, w, packed, B, T, L, KX, H);
+    const int nlaunch = T + 2 * L - 1;
+    hipStream_t st = (hipStream_t)stream;
+    if (stack_hoists_input(KX, H)) {
+        if (!aligned16(x)) return fail(OPNET_EINVAL, "x must be 16-byte aligned");
+        stack_hoisted_input_tiled(x, packed, w, (float4 *)(w + W.xg), B, T, L, KX, H, st);
         rows_to_packed<<<2048, 256, 0, st>>>(x, (float4 *)(w + W.xp), B, T, RB, 0, 0, (float4 *)(w + W.state),
                                               (long)((W.state_end - W.state) / 16));      // zero the state only
     } else {
         rows_to_packed<<<2048, 256, 0, st>>>(x, (float4 *)(w + W.xp), B, T, RB, KX, P.nhx[0] * 16,
                                               (float4 *)(w + W.state), (long)((W.state_end - W.state) / 16));
     }
-    const dim3 grid((ntiles + 7) / 8 * 8, RB < OPNET_MAX_GY ? RB : OPNET_MAX_GY, 1);   // XCD-aligned, see step_grid
     if (!graph) {
         const stack_step_fn stepk = stack_step_kernel(RB);
         for (int s = 0; s < nlaunch; ++s) stepk<<<grid, stack_step_threads(RB), 0, st>>>(a, s);
@@ -3007,6 +3032,7 @@ extern "C" int opseq_encoder_layer_batched_f32(float *z, const float *in_w, cons
 
 #include "enc_train_abi.hip"
 #include "opnet_stream_abi.hip"
+#include "seq_stream_abi.hip"
 
 // ------------------------------------------------------------------------------------------------
 // detector backbone primitives (NHWC fp32)

@@ -1,0 +1,125 @@
+// seq_stream_abi.hip - host side of the stateful stacked-LSTM streams (C ABI: opseq_stream_*; kernels in
+// seq_stream_kernels.hip).  Included by opnet_abi.hip (one translation unit: it uses that file's fail / HIP_TRY / env_int /
+// aligned16 and the launch chain's check_stack / stack_args_inference / stack_hoisted_input_tiled / stack_step_kernel).
+#pragma once
+
+// The skinny input product computes every 16-clip fragment of every frame that holds a live stream: k * ceil(n / 16) * 16
+// rows, each fragment re-reading its 16 W_ih0 rows.  Calls of at most SEQ_STREAM_SKINNY_MAX_ROWS such rows take it; larger
+// ones the tiled GEMM, which gives the same bits.  Measured on the MI355X (tools/stream_bench.py --model non_linear_lstm,
+// DESIGN.md 12b): the product alone 223 against 289 us at 512 such rows, 443 against 293 us at 1 024.
+// OPSEQ_STREAM_SKINNY_MAX_ROWS overrides it at call time; 0 = always the tiled GEMM.
+#define SEQ_STREAM_SKINNY_MAX_ROWS 512
+#define SEQ_STREAM_SKINNY_DEPTH 16       // K steps of 16 whose operands a wave keeps in flight
+
+static long seq_stream_skinny_rows(int n, int k) { return (long)k * ((n + 15) / 16) * 16; }
+
+// the hoisted layer-0 input product into xg [k][RB][H][32] float4: skinny (one wave per 16 x 16 fragment of xg, row fragments
+// in its [t][rb][clip] order, the waves of a workgroup along rows over one column fragment) or the tiled GEMM + repack (its G
+// in the workspace w)
+static void seq_stream_input_product(const float *x, const float *packed, float4 *xg, char *w, int n, int k, int L, int KX,
+                                     int H, bool skinny, hipStream_t st)
+{
+    if (skinny) {
+        const StackPackedLayout P = stack_packed_layout(L, KX, H);
+        const int RB = (n + 31) / 32;
+        const long frags = (long)k * RB * 2;
+        const int nw = frags < 4 ? (int)frags : 4;
+        seq_stream_input_skinny<SEQ_STREAM_SKINNY_DEPTH><<<dim3((unsigned)((frags + nw - 1) / nw), H / 4), nw * 64, 0, st>>>(
+            x, packed + P.wih0g, xg, n, k, RB, KX, H);
+        return;
+    }
+    stack_hoisted_input_tiled(x, packed, w, xg, n, k, L, KX, H, st);
+}
+
+static bool seq_stream_takes_skinny(int n, int k)
+{
+    return seq_stream_skinny_rows(n, k) <= env_int("OPSEQ_STREAM_SKINNY_MAX_ROWS", SEQ_STREAM_SKINNY_MAX_ROWS);
+}
+
+static int check_seq_stream(int n, int k, int L, int KX, int H)
+{
+    if (int rc = check_stack(n, k, L, KX, H)) return rc;
+    if ((n + 31) / 32 > 65535) return fail(OPNET_ESHAPE, "n=%d streams exceed one call's 65535 row blocks", n);
+    return OPNET_OK;
+}
+
+extern "C" size_t opseq_stream_state_floats(int L, int H)
+{
+    if (check_stack(1, 1, L, 1, H)) return 0;
+    return 2 * (size_t)L * H;
+}
+
+// the chain's inference workspace for n clips x k frames: the skinny product writes xg directly and leaves the chain's G
+// buffer unused, but a call may still take the tiled GEMM (OPSEQ_STREAM_SKINNY_MAX_ROWS), so the size stays the chain's
+extern "C" size_t opseq_stream_workspace_bytes(int n, int k, int L, int KX, int H)
+{
+    if (check_seq_stream(n, k, L, KX, H)) return 0;
+    return stack_workspace_layout(n, k, L, KX, H).total;
+}
+
+// [hoisted input product] -> prologue -> k + 2L - 1 step launches -> write-back, dependent launches on `stream`, no host
+// synchronisation
+extern "C" int opseq_stream_step_f32(const float *x, const int32_t *slots, float *state, const float *packed, float *y,
+                                     void *workspace, size_t workspace_bytes, int n, int k, int capacity, int L, int KX,
+                                     int H, void *stream)
+{
+    if (int rc = check_seq_stream(n, k, L, KX, H)) return rc;
+    if (capacity <= 0) return fail(OPNET_ESHAPE, "capacity=%d must be positive", capacity);
+    if (!x || !slots || !state || !packed || !y || !workspace) return fail(OPNET_EINVAL, "null pointer");
+    const bool hoist = stack_hoists_input(KX, H);
+    if (!aligned16(state) || !aligned16(packed) || !aligned16(y) || !aligned16(workspace) || (((uintptr_t)slots) & 3u) ||
+        (((uintptr_t)x) & (hoist ? 15u : 3u)))
+        return fail(OPNET_EINVAL, "state/packed/y/workspace must be 16-byte aligned, slots 4-byte and x %d-byte",
+                    hoist ? 16 : 4);
+    const StackWorkspaceLayout W = stack_workspace_layout(n, k, L, KX, H);
+    if (workspace_bytes < W.total) return fail(OPNET_EWORKSPACE, "workspace %zu B < %zu B", workspace_bytes, W.total);
+
+    char *w = (char *)workspace;
+    SeqStreamArgs s;
+    memset(&s, 0, sizeof(s));
+    const dim3 grid = stack_args_inference(&s.a, w, packed, n, k, L, KX, H);
+    s.x = x;
+    s.slots = slots;
+    s.state = state;
+    s.y = y;
+    s.xp = (float4 *)(w + W.xp);
+    s.KX = KX;
+    s.KQ = hoist ? 0 : stack_packed_layout(L, KX, H).nhx[0] * 4;
+    s.capacity = capacity;
+    const StackArgs &a = s.a;
+    hipStream_t st = (hipStream_t)stream;
+
+    if (hoist)
+        seq_stream_input_product(x, packed, (float4 *)(w + W.xg), w, n, k, L, KX, H, seq_stream_takes_skinny(n, k), st);
+    // gather workgroups per row block: one work item per (layer, unit quad, clip), up to 256 a thread
+    const int gather_items = L * (H / 4) * 32;
+    const int G = (gather_items + 255) / 256 < 64 ? (gather_items + 255) / 256 : 64;
+    seq_stream_prologue<<<dim3((hoist ? 0 : k) + G, a.RB), 256, 0, st>>>(s);
+    const stack_step_fn stepk = stack_step_kernel(a.RB);
+    for (int t = 0; t < k + 2 * L - 1; ++t) stepk<<<grid, stack_step_threads(a.RB), 0, st>>>(a, t);
+    const long items = (long)n * k > (long)a.RB * 32 * L * (H / 4) ? (long)n * k : (long)a.RB * 32 * L * (H / 4);
+    const unsigned wb = (unsigned)((items + 255) / 256 > 1024 ? 1024 : (items + 255) / 256);
+    seq_stream_writeback<<<wb, 256, 0, st>>>(s);
+    HIP_TRY(hipGetLastError());
+    return OPNET_OK;
+}
+
+// the hoisted layer-0 input product of a stream call alone, into the caller's xg: route 0 = as opseq_stream_step_f32 routes
+// it, 1 = the skinny kernel, 2 = the tiled GEMM + repack (workspace: opseq_stream_workspace_bytes)
+extern "C" int opseq_stream_input_product_f32(const float *x, const float *packed, float *xg, void *workspace,
+                                              size_t workspace_bytes, int n, int k, int L, int KX, int H, int route, void *stream)
+{
+    if (int rc = check_seq_stream(n, k, L, KX, H)) return rc;
+    if (!stack_hoists_input(KX, H))
+        return fail(OPNET_EINVAL, "layer 0's input is not hoisted (KX=%d H=%d: needs KX %% 16 == 0 and KX >= 2H)", KX, H);
+    if (route < 0 || route > 2) return fail(OPNET_EINVAL, "route must be 0, 1 or 2 (got %d)", route);
+    if (!x || !packed || !xg || !workspace) return fail(OPNET_EINVAL, "null pointer");
+    if (!aligned16(x) || !aligned16(packed) || !aligned16(xg) || !aligned16(workspace))
+        return fail(OPNET_EINVAL, "x/packed/xg/workspace must be 16-byte aligned");
+    const size_t need = stack_workspace_layout(n, k, L, KX, H).total;
+    if (workspace_bytes < need) return fail(OPNET_EWORKSPACE, "workspace %zu B < %zu B", workspace_bytes, need);
+    const bool skinny = route == 0 ? seq_stream_takes_skinny(n, k) : route == 1;
+    seq_stream_input_product(x, packed, (float4 *)xg, (char *)workspace, n, k, L, KX, H, skinny, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return OPNET_OK;
+}

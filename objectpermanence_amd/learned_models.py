@@ -879,12 +879,10 @@ class _LstmStackRunner:
             return self._run_xcd(x, ws_list, head)
         return self._run_chain(x, ws_list, head)
 
-    def _run_chain(self, x: torch.Tensor, ws_list, head: "LinearWeight") -> torch.Tensor:
-        """one launch per time step (csrc/seq_kernels.hip lstm_stack_step), T + 2 L - 1 launches as one hipGraph"""
+    def _packed_weights(self, ws_list, dev: torch.device, stream: int) -> torch.Tensor:
+        """the launch chain's packed image (opseq_lstm_stack_pack_weights_f32) of ws_list = [w_ih_0..L-1, w_hh_0..L-1, head]
+        for `stream`, re-packed on it whenever a weight changed since the last pack"""
         lib = _lib.load()
-        dev = x.device
-        B, T = int(x.shape[0]), int(x.shape[1])
-        stream = _stream_ptr(dev)
         key = _weights_key(ws_list, dev)
         # packed image and workspace PER STREAM (as _run_xcd): a server issues a segmented model's passes on two side streams in
         # turn - a pass on stream B must neither read an image stream A is still packing nor share A's workspace
@@ -905,11 +903,20 @@ class _LstmStackRunner:
             arr = _lib.c_void_p * self.L
             ih = arr(*[w.data_ptr() for w in ws_list[:self.L]])
             hh = arr(*[w.data_ptr() for w in ws_list[self.L:2 * self.L]])
-            rc = lib.opseq_lstm_stack_pack_weights_f32(ih, hh, head.weight.data_ptr(), buf.data_ptr(), nbytes,
+            rc = lib.opseq_lstm_stack_pack_weights_f32(ih, hh, ws_list[2 * self.L].data_ptr(), buf.data_ptr(), nbytes,
                                                        self.L, self.KX, self.H, stream)
             _lib.check(rc, "opseq_lstm_stack_pack_weights_f32")
             self._cpacked[stream] = (key, buf)
-        self.packed, self.key = self._cpacked[stream][1], key
+        return self._cpacked[stream][1]
+
+    def _run_chain(self, x: torch.Tensor, ws_list, head: "LinearWeight") -> torch.Tensor:
+        """one launch per time step (csrc/seq_kernels.hip lstm_stack_step), T + 2 L - 1 launches as one hipGraph"""
+        lib = _lib.load()
+        dev = x.device
+        B, T = int(x.shape[0]), int(x.shape[1])
+        stream = _stream_ptr(dev)
+        self.packed = self._packed_weights(ws_list, dev, stream)
+        self.key = self._cpacked[stream][0]
         wkey = (B, T, str(dev), stream)
         if wkey not in self.ws:
             nb = lib.opseq_lstm_stack_workspace_bytes(B, T, self.L, self.KX, self.H)

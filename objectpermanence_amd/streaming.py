@@ -12,6 +12,17 @@ kernels, so any chunking of a clip gives the bits of the whole-clip launch-chain
     h1, c1, h2, c2 = streams.get_state(ids)        # [1, n, H] each (nn.LSTM's h_n / c_n); OPNetLstmMlp: h2 = c2 = None
     streams.set_state(ids, h1, c1, h2, c2)
     streams.close(ids)
+
+`LstmStackStreams` does the same for the stacked-LSTM reasoners BaselineLstm and NonLinearLstm (and their `_no_labels`
+variants), through opseq_stream_step_f32 and the stacked launch chain's own step kernel:
+
+    streams = LstmStackStreams(model, capacity=1024)
+    ids = streams.open(3)
+    y = streams.step(ids, x)                       # x [n, k, 15, 5] -> y [n, k, 4]
+    h_n, c_n = streams.get_state(ids)              # [L, n, H] each (nn.LSTM's h_n / c_n)
+    streams.set_state(ids, h_n, c_n)
+
+TransformerLstm is not streamed: its encoder attends over the whole sequence, so a frame's output depends on later frames.
 """
 from __future__ import annotations
 
@@ -21,7 +32,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .learned_models import OPNet, OPNetLstmMlp, _stream_ptr
+from .learned_models import BaselineLstm, NonLinearLstm, OPNet, OPNetLstmMlp, _stream_ptr
 
 
 class StreamSlots:
@@ -73,37 +84,32 @@ class StreamSlots:
         return idx
 
 
-class OPNetStreams:
-    """A pool of `capacity` OPNet (or OPNetLstmMlp) streams on the model's ROCm device.  Calls are enqueued on the
-    current torch stream and are inference only (no autograd graph).  The model's own packed weight image is used, so an
-    in-place parameter update takes effect on the next call."""
+class _StreamPool:
+    """What every stream pool shares: the model's ROCm device, the slot bookkeeping, the state pool (one row of `row`
+    floats per slot, zero at open) and the per-(n, k, stream) workspaces."""
 
     MAX_WORKSPACES = 8       # (n, k, stream) workspaces kept alive, least recently used dropped first
 
-    def __init__(self, model, capacity: int = 1024):
-        if isinstance(model, OPNet):
-            self._mlp = 0
-        elif isinstance(model, OPNetLstmMlp):
-            self._mlp = 1
-        else:
-            raise TypeError(f"OPNetStreams serves OPNet and OPNetLstmMlp, not {type(model).__name__} (the other reasoners "
-                            "are not streamed: transformer_lstm's encoder attends over the whole sequence)")
+    def __init__(self, model, capacity: int):
         slots = StreamSlots(capacity)
         dev = next(model.parameters()).device
         if dev.type != "cuda":
-            raise RuntimeError("OPNetStreams runs on MI355X only: move the model to a ROCm device first; there is no CPU "
-                               "fallback")
-        lib = _lib.load()
+            raise RuntimeError(f"{type(self).__name__} runs on MI355X only: move the model to a ROCm device first; there is "
+                               "no CPU fallback")
         self.model = model
         self.device = dev
         self.slots = slots
         self.capacity = slots.capacity
-        self.H1, self.H2 = model._h1, model._h2
-        self._row = int(lib.opnet_stream_state_floats(self.H1, self.H2))
-        if self._row == 0:
-            _lib.check(-2, "opnet_stream_state_floats")
-        self.state = torch.zeros((self.capacity, self._row), dtype=torch.float32, device=dev)
         self._ws: Dict[Tuple[int, int, int], torch.Tensor] = {}
+
+    def _alloc_state(self, row: int, what: str) -> None:
+        if row == 0:
+            _lib.check(-2, what)
+        self._row = int(row)
+        self.state = torch.zeros((self.capacity, self._row), dtype=torch.float32, device=self.device)
+
+    def _workspace_bytes(self, n: int, k: int) -> int:
+        raise NotImplementedError
 
     # -- slots --------------------------------------------------------------------------------
     @property
@@ -119,6 +125,44 @@ class OPNetStreams:
 
     def close(self, ids: Sequence[int]) -> None:
         self.slots.close(ids)
+
+    def _workspace(self, n: int, k: int, stream: int) -> torch.Tensor:
+        # one per (n, k, stream): calls on different streams must not share one.  A dropped workspace may still be read
+        # by launches on its stream; the caching allocator only hands the block back to that stream, behind them.
+        key = (n, k, stream)
+        ws = self._ws.pop(key, None)
+        if ws is None:
+            nbytes = self._workspace_bytes(n, k)
+            while len(self._ws) >= self.MAX_WORKSPACES:
+                self._ws.pop(next(iter(self._ws)))
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        self._ws[key] = ws          # most recently used at the end
+        return ws
+
+
+class OPNetStreams(_StreamPool):
+    """A pool of `capacity` OPNet (or OPNetLstmMlp) streams on the model's ROCm device.  Calls are enqueued on the
+    current torch stream and are inference only (no autograd graph).  The model's own packed weight image is used, so an
+    in-place parameter update takes effect on the next call."""
+
+    def __init__(self, model, capacity: int = 1024):
+        if isinstance(model, OPNet):
+            self._mlp = 0
+        elif isinstance(model, OPNetLstmMlp):
+            self._mlp = 1
+        else:
+            raise TypeError(f"OPNetStreams serves OPNet and OPNetLstmMlp, not {type(model).__name__} (BaselineLstm and "
+                            "NonLinearLstm are streamed by LstmStackStreams; transformer_lstm is not streamed: its encoder "
+                            "attends over the whole sequence)")
+        super().__init__(model, capacity)
+        self.H1, self.H2 = model._h1, model._h2
+        self._alloc_state(_lib.load().opnet_stream_state_floats(self.H1, self.H2), "opnet_stream_state_floats")
+
+    def _workspace_bytes(self, n: int, k: int) -> int:
+        nbytes = _lib.load().opnet_stream_workspace_bytes(n, k, self.H1, self.H2)
+        if nbytes == 0:
+            _lib.check(-2, "opnet_stream_workspace_bytes")
+        return nbytes
 
     # -- state --------------------------------------------------------------------------------
     def get_state(self, ids: Sequence[int]):
@@ -189,17 +233,91 @@ class OPNetStreams:
             _lib.check(rc, "opnet_stream_step_f32")
         return y, logits
 
-    def _workspace(self, n: int, k: int, stream: int) -> torch.Tensor:
-        # one per (n, k, stream): calls on different streams must not share one.  A dropped workspace may still be read
-        # by launches on its stream; the caching allocator only hands the block back to that stream, behind them.
-        key = (n, k, stream)
-        ws = self._ws.pop(key, None)
-        if ws is None:
-            nbytes = _lib.load().opnet_stream_workspace_bytes(n, k, self.H1, self.H2)
-            if nbytes == 0:
-                _lib.check(-2, "opnet_stream_workspace_bytes")
-            while len(self._ws) >= self.MAX_WORKSPACES:
-                self._ws.pop(next(iter(self._ws)))
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-        self._ws[key] = ws          # most recently used at the end
-        return ws
+
+class LstmStackStreams(_StreamPool):
+    """A pool of `capacity` BaselineLstm (or NonLinearLstm) streams on the model's ROCm device.  Calls are enqueued on the
+    current torch stream and are inference only (no autograd graph).  The model's own packed weight image (the launch
+    chain's, _LstmStackRunner._packed_weights) is used, so an in-place parameter update takes effect on the next call.
+    A stream's state row is [h_0 | c_0 | h_1 | c_1 ...] over the model's L layers."""
+
+    def __init__(self, model, capacity: int = 1024):
+        if isinstance(model, NonLinearLstm):
+            self._embed = True
+        elif isinstance(model, BaselineLstm):
+            self._embed = False
+        else:
+            raise TypeError(f"LstmStackStreams serves BaselineLstm and NonLinearLstm, not {type(model).__name__} (OPNet and "
+                            "OPNetLstmMlp are streamed by OPNetStreams; transformer_lstm is not streamed: its encoder "
+                            "attends over the whole sequence, so it is not causal)")
+        super().__init__(model, capacity)
+        r = model._runner
+        self.L, self.KX, self.H = r.L, r.KX, r.H
+        self.slots_per_frame, self.features = model.max_objects_in_frame, model.bb_in_dim
+        self._alloc_state(_lib.load().opseq_stream_state_floats(self.L, self.H), "opseq_stream_state_floats")
+
+    def _workspace_bytes(self, n: int, k: int) -> int:
+        nbytes = _lib.load().opseq_stream_workspace_bytes(n, k, self.L, self.KX, self.H)
+        if nbytes == 0:
+            _lib.check(-2, "opseq_stream_workspace_bytes")
+        return nbytes
+
+    # -- state --------------------------------------------------------------------------------
+    def get_state(self, ids: Sequence[int]):
+        """(h_n, c_n) of the streams, [L, n, H] each in nn.LSTM's (num_layers, batch, hidden) layout; copies"""
+        idx = self.slots.check(ids)
+        with torch.cuda.device(self.device):
+            rows = self.state.index_select(0, torch.from_numpy(idx).to(self.device))
+        rows = rows.view(idx.size, self.L, 2, self.H)
+        return rows[:, :, 0].transpose(0, 1).contiguous(), rows[:, :, 1].transpose(0, 1).contiguous()
+
+    def set_state(self, ids: Sequence[int], h_n: torch.Tensor, c_n: torch.Tensor) -> None:
+        """overwrite the state of open streams with nn.LSTM-shaped [L, n, H] tensors"""
+        idx = self.slots.check(ids)
+        n = idx.size
+        for t, name in ((h_n, "h_n"), (c_n, "c_n")):
+            if tuple(t.shape) != (self.L, n, self.H):
+                raise ValueError(f"{name} must be [{self.L}, {n}, {self.H}], got {tuple(t.shape)}")
+        with torch.cuda.device(self.device):
+            h = h_n.to(device=self.device, dtype=torch.float32).transpose(0, 1)
+            c = c_n.to(device=self.device, dtype=torch.float32).transpose(0, 1)
+            rows = torch.stack([h, c], dim=2).reshape(n, self._row)
+            self.state.index_copy_(0, torch.from_numpy(idx).to(self.device), rows)
+
+    # -- frames -------------------------------------------------------------------------------
+    def step(self, ids: Sequence[int], x: torch.Tensor) -> torch.Tensor:
+        """advance the streams `ids` by k frames: x [n, k, 15, 5] (row i belongs to ids[i]) -> y [n, k, 4], the outputs
+        of those frames"""
+        if not isinstance(x, torch.Tensor) or not x.is_cuda:
+            raise RuntimeError("LstmStackStreams.step runs on MI355X only: `x` must be a tensor on a ROCm device")
+        if x.device != self.device:
+            raise ValueError(f"x is on {x.device}, the stream pool on {self.device}")
+        idx = self.slots.check(ids)
+        n = idx.size
+        S, F = self.slots_per_frame, self.features
+        if x.dim() != 4 or x.shape[0] != n or x.shape[2] != S or x.shape[3] != F or x.shape[1] < 1:
+            raise ValueError(f"x must be [n={n}, k>=1, {S}, {F}], got {tuple(x.shape)}")
+        k = int(x.shape[1])
+        m = self.model
+        lib = _lib.load()
+        with torch.no_grad(), torch.cuda.device(self.device):
+            x = x.contiguous().float()
+            stream = _stream_ptr(self.device)
+            if self._embed:      # relu(Linear 5 -> F) per slot, as NonLinearLstm.forward
+                feats = torch.empty((n, k, self.KX), dtype=torch.float32, device=self.device)
+                rc = lib.opseq_slot_embed_relu_f32(x.data_ptr(), m.boxes_linear.weight.data_ptr(), feats.data_ptr(), n * k, S,
+                                                   self.KX // S, stream)
+                _lib.check(rc, "opseq_slot_embed_relu_f32")
+            else:
+                feats = x
+            lstm, head = m.video_LSTM, m.predictions_layer
+            ws_list = [getattr(lstm, f"weight_ih_l{l}") for l in range(self.L)] + \
+                      [getattr(lstm, f"weight_hh_l{l}") for l in range(self.L)] + [head.weight]
+            packed = m._runner._packed_weights(ws_list, self.device, stream)
+            ws = self._workspace(n, k, stream)
+            slots = torch.from_numpy(idx.astype(np.int32)).to(self.device)      # one small H2D copy on this stream
+            y = torch.empty((n, k, 4), dtype=torch.float32, device=self.device)
+            rc = lib.opseq_stream_step_f32(feats.data_ptr(), slots.data_ptr(), self.state.data_ptr(), packed.data_ptr(),
+                                           y.data_ptr(), ws.data_ptr(), ws.numel(), n, k, self.capacity, self.L, self.KX,
+                                           self.H, stream)
+            _lib.check(rc, "opseq_stream_step_f32")
+        return y

@@ -7,7 +7,12 @@ default engine: that forward is also what "recompute the prefix each frame" cost
 prefix_speedup = (default-engine forward at T = 300) / (one k = 1 stream call).  abi_k1: the one-frame call through the
 C ABI with its buffers prepared, i.e. without OPNetStreams' per-call Python work.  Prints one JSON object.
 
-    python tools/stream_bench.py [--ns 1,32,256] [--ks 1,8,300] [--out result.json]
+--model baseline_lstm / non_linear_lstm times LstmStackStreams the same way (H = 512; NonLinearLstm F = 256).  For
+non_linear_lstm it also times the hoisted input product alone through both routes in the same run (the skinny kernel and
+the tiled GEMM + repack, alternating windows; HIP events around opseq_stream_input_product_f32), at n x k from one stream to
+32 x 32 rows, small n with large k included.
+
+    python tools/stream_bench.py [--model opnet] [--ns 1,32,256] [--ks 1,8,300] [--out result.json]
 """
 import argparse
 import json
@@ -45,12 +50,22 @@ def _time(fn, calls, warmup=3):
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--model", default="opnet", choices=["opnet", "baseline_lstm", "non_linear_lstm"])
     ap.add_argument("--ns", default="1,32,256")
     ap.add_argument("--ks", default="1,8,300")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("stream_bench.py needs a ROCm device")
+    res = bench_opnet(args) if args.model == "opnet" else bench_stack(args)
+    line = json.dumps(res)
+    print(line)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+
+
+def bench_opnet(args):
     from objectpermanence_amd import ModelsFactory, OPNetStreams, _lib
     dev = "cuda:0"
     m = ModelsFactory.get_model("opnet", CFG)
@@ -99,11 +114,107 @@ def main():
             row["prefix_speedup_vs_chain_at_t300"] = round(row["whole_clip_chain"]["device_us"] / row["stream_k1"]["device_us"], 1)
         res["rows"].append(row)
         print(json.dumps(row), file=sys.stderr, flush=True)
-    line = json.dumps(res)
-    print(line)
-    if args.out:
-        with open(args.out, "w") as f:
-            f.write(line + "\n")
+    return res
+
+
+STACK_CFG = {"baseline_lstm": {"videos_hidden_dim": 512},
+             "non_linear_lstm": {"boxes_features_dim": 256, "videos_hidden_dim": 512}}
+STACK_PARAMS = {"baseline_lstm": synth.baseline_lstm_synth_params, "non_linear_lstm": synth.non_linear_lstm_synth_params}
+
+
+def bench_stack(args):
+    from objectpermanence_amd import LstmStackStreams, ModelsFactory, _lib
+    dev = "cuda:0"
+    cfg = STACK_CFG[args.model]
+    m = ModelsFactory.get_model(args.model, cfg)
+    m.load_state_dict({k: torch.from_numpy(v.copy()) for k, v in STACK_PARAMS[args.model](cfg).items()})
+    m.eval().to(dev)
+    r = m._runner
+    L, KX, H = r.L, r.KX, r.H
+    ns = [int(v) for v in args.ns.split(",")]
+    ks = [int(v) for v in args.ks.split(",")]
+    res = {"device": torch.cuda.get_device_name(0), "model": args.model, "L": L, "KX": KX, "H": H, "T_whole_clip": T,
+           "rows": []}
+    lib = _lib.load()
+    stream = torch.cuda.current_stream().cuda_stream
+    for n in ns:
+        x5 = torch.from_numpy(synth.boxes5(synth.make_batch(0, n, T)[0])).to(dev)
+        row = {"n": n}
+        with torch.no_grad():
+            r.use_xcd = "0"
+            row["whole_clip_chain"] = _time(lambda: m(x5), 5, warmup=2)
+            r.use_xcd = "auto"
+            row["whole_clip_default"] = _time(lambda: m(x5), 5, warmup=2)
+            row["whole_clip_default_engine"] = r.engine(n, T)
+        streams = LstmStackStreams(m, capacity=n)
+        ids = streams.open(n)
+        for k in ks:
+            x = x5[:, :k].contiguous()
+            calls = max(5, min(200, 1200 // k))
+            row[f"stream_k{k}"] = _time(lambda: streams.step(ids, x), calls)
+            row[f"stream_k{k}"]["device_us_per_frame"] = round(row[f"stream_k{k}"]["device_us"] / k, 2)
+        # the one-frame call straight through the C ABI with every buffer prepared (NonLinearLstm: its layer-0 input already
+        # embedded): the LSTM's kernels without the Python work of LstmStackStreams.step
+        if 1 in ks:
+            feats = torch.randn((n, 1, KX), device=dev).abs()
+            slots = torch.tensor(ids, dtype=torch.int32, device=dev)
+            y1 = torch.empty((n, 1, 4), device=dev)
+            ws = torch.empty(lib.opseq_stream_workspace_bytes(n, 1, L, KX, H), dtype=torch.uint8, device=dev)
+            wl = [getattr(m.video_LSTM, f"weight_ih_l{l}") for l in range(L)] + \
+                 [getattr(m.video_LSTM, f"weight_hh_l{l}") for l in range(L)] + [m.predictions_layer.weight]
+            packed = r._packed_weights(wl, torch.device(dev), stream)
+
+            def abi_call():
+                _lib.check(lib.opseq_stream_step_f32(feats.data_ptr(), slots.data_ptr(), streams.state.data_ptr(),
+                                                     packed.data_ptr(), y1.data_ptr(), ws.data_ptr(), ws.numel(), n, 1, n, L, KX,
+                                                     H, stream), "opseq_stream_step_f32")
+            row["abi_k1"] = _time(abi_call, 200)
+        if 300 in ks:
+            row["k300_over_chain"] = round(row["stream_k300"]["device_us"] / row["whole_clip_chain"]["device_us"], 3)
+        if 1 in ks:
+            row["prefix_speedup_at_t300"] = round(row["whole_clip_default"]["device_us"] / row["stream_k1"]["device_us"], 1)
+            row["prefix_speedup_vs_chain_at_t300"] = round(row["whole_clip_chain"]["device_us"] / row["stream_k1"]["device_us"], 1)
+        res["rows"].append(row)
+        print(json.dumps(row), file=sys.stderr, flush=True)
+    if args.model == "non_linear_lstm":
+        res["input_product"] = bench_input_product(m, dev)
+    return res
+
+
+PRODUCT_SHAPES = [(1, 1), (32, 1), (1, 32), (32, 8), (32, 16), (1, 300), (5, 64), (32, 32), (256, 1)]
+
+
+def bench_input_product(m, dev, rounds=4):
+    """the hoisted layer-0 input product alone (opseq_stream_input_product_f32): the skinny kernel against the tiled GEMM +
+    repack at n streams x k frames, in alternating windows of 50 launches; rows_skinny = the k * ceil(n / 16) * 16 rows the
+    skinny kernel computes (what the router compares with OPSEQ_STREAM_SKINNY_MAX_ROWS)"""
+    from objectpermanence_amd import _lib
+    lib = _lib.load()
+    r = m._runner
+    L, KX, H = r.L, r.KX, r.H
+    stream = torch.cuda.current_stream().cuda_stream
+    wl = [getattr(m.video_LSTM, f"weight_ih_l{l}") for l in range(L)] + \
+         [getattr(m.video_LSTM, f"weight_hh_l{l}") for l in range(L)] + [m.predictions_layer.weight]
+    packed = r._packed_weights(wl, torch.device(dev), stream)
+    out = []
+    for n, k in PRODUCT_SHAPES:
+        x = torch.rand((n, k, KX), device=dev)
+        xg = torch.empty((k, (n + 31) // 32, H, 32, 4), device=dev)
+        ws = torch.empty(lib.opseq_stream_workspace_bytes(n, k, L, KX, H), dtype=torch.uint8, device=dev)
+
+        def product(route):
+            _lib.check(lib.opseq_stream_input_product_f32(x.data_ptr(), packed.data_ptr(), xg.data_ptr(), ws.data_ptr(),
+                                                          ws.numel(), n, k, L, KX, H, route, stream),
+                       "opseq_stream_input_product_f32")
+        times = {"skinny": [], "tiled": []}
+        for _ in range(rounds):
+            for route, code in (("skinny", 1), ("tiled", 2)):
+                times[route].append(_time(lambda: product(code), 50)["device_us"])
+        skinny, tiled = min(times["skinny"]), min(times["tiled"])
+        out.append({"n": n, "k": k, "rows": n * k, "rows_skinny": k * ((n + 15) // 16) * 16, "skinny_us": skinny,
+                    "tiled_us": tiled, "tiled_over_skinny": round(tiled / skinny, 2), "windows": times})
+        print(json.dumps(out[-1]), file=sys.stderr, flush=True)
+    return out
 
 
 if __name__ == "__main__":
