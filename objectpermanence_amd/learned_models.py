@@ -16,6 +16,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from ._device_cache import PackedImages, TrainingBuffers, Workspaces, check_weights
 from .launch_monitor import LaunchMonitor
 
 
@@ -85,25 +86,14 @@ class _OPNetTrainFunction(torch.autograd.Function):
         h1, h2 = module._h1, module._h2
         with torch.cuda.device(dev):
             stream = _stream_ptr(dev)
-            nbytes = lib.opnet_train_packed_weights_bytes(h1, h2)
-            if module._tpacked is None or module._tpacked.device != dev:
-                module._tpacked = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
-            rc = lib.opnet_train_pack_weights_f32(*(w.data_ptr() for w in weights), module._tpacked.data_ptr(),
-                                                  nbytes, h1, h2, stream)
-            _lib.check(rc, "opnet_train_pack_weights_f32")
-            key = (B, T, str(dev))
-            if module._tws_key != key:
-                wsb = lib.opnet_train_workspace_bytes(B, T, h1, h2)
-                if wsb == 0:
-                    _lib.check(-2, "opnet_train_workspace_bytes")
-                module._tws = None          # release the old history first
-                module._tws = torch.empty(wsb, dtype=torch.uint8, device=dev)
-                module._tws_key = key
+            packed = module._train.packed(dev, (lib.opnet_train_packed_weights_bytes, h1, h2), lambda buf, n: _lib.check(
+                lib.opnet_train_pack_weights_f32(*(w.data_ptr() for w in weights), buf.data_ptr(), n, h1, h2, stream),
+                "opnet_train_pack_weights_f32"))
+            tws = module._train.history_for(B, T, dev, (lib.opnet_train_workspace_bytes, B, T, h1, h2))
             y = torch.empty((B, T, 4), dtype=torch.float32, device=dev)
             logits = torch.empty((B, 15, T), dtype=torch.float32, device=dev)
-            rc = lib.opnet_train_forward_f32(boxes.data_ptr(), module._tpacked.data_ptr(), y.data_ptr(),
-                                             logits.data_ptr(), module._tws.data_ptr(), module._tws.numel(),
-                                             B, T, h1, h2, stream)
+            rc = lib.opnet_train_forward_f32(boxes.data_ptr(), packed.data_ptr(), y.data_ptr(), logits.data_ptr(),
+                                             tws.data_ptr(), tws.numel(), B, T, h1, h2, stream)
             _lib.check(rc, "opnet_train_forward_f32")
         module._train_gen += 1
         ctx.module, ctx.gen, ctx.shape = module, module._train_gen, (B, T)
@@ -137,16 +127,16 @@ class _OPNetTrainFunction(torch.autograd.Function):
             grads = [bucket.view(i) for i in range(len(ctx.wshapes))]
         else:
             grads = [torch.empty(s, dtype=torch.float32, device=dev) for s in ctx.wshapes]
+        tb = module._train
         with torch.cuda.device(dev):
-            rc = lib.opnet_train_backward_f32(grad_y.data_ptr(), module._tpacked.data_ptr(), module._tws.data_ptr(),
-                                              module._tws.numel(), *(g.data_ptr() for g in grads), B, T,
-                                              module._h1, module._h2, _stream_ptr(dev))
+            rc = lib.opnet_train_backward_f32(grad_y.data_ptr(), tb.image.data_ptr(), tb.history.data_ptr(), tb.history.numel(),
+                                              *(g.data_ptr() for g in grads), B, T, module._h1, module._h2, _stream_ptr(dev))
         _lib.check(rc, "opnet_train_backward_f32")
         # the abort words of the step's two persistent launches (sticky from the forward): mirrored to the host behind the
         # backward; training.finish_step / OPNet.training_step_aborted() look at them at the caller's next sync point
         off = lib.opnet_train_status_offset(B, T, module._h1, module._h2)
         if off != _lib.NO_OFFSET and lib.opnet_xcd4_enabled():
-            module._monitor.watch(module._tws, off, module._note_training_abort, "opnet_xcd4_forward/backward (training step)")
+            module._monitor.watch(tb.history, off, module._note_training_abort, "opnet_xcd4_forward/backward (training step)")
         return (None, None) + tuple(grads)
 
 
@@ -161,28 +151,15 @@ class _OPNetMlpTrainFunction(torch.autograd.Function):
         h1, h2 = module._h1, module._h2
         with torch.cuda.device(dev):
             stream = _stream_ptr(dev)
-            nbytes = lib.opnet_train_packed_weights_bytes(h1, h2)
-            if nbytes == 0:
-                _lib.check(-2, "opnet_train_packed_weights_bytes")
-            if module._tpacked is None or module._tpacked.device != dev:
-                module._tpacked = torch.zeros(nbytes // 4, dtype=torch.float32, device=dev)
-                module._tscratch = torch.empty(4 * h2 * 6, dtype=torch.float32, device=dev)
-            rc = lib.opnet_mlp_train_pack_weights_f32(*(w.data_ptr() for w in weights), module._tpacked.data_ptr(),
-                                                      nbytes, module._tscratch.data_ptr(), h1, h2, stream)
-            _lib.check(rc, "opnet_mlp_train_pack_weights_f32")
-            key = (B, T, str(dev))
-            if module._tws_key != key:
-                wsb = lib.opnet_train_workspace_bytes(B, T, h1, h2)
-                if wsb == 0:
-                    _lib.check(-2, "opnet_train_workspace_bytes")
-                module._tws = None
-                module._tws = torch.empty(wsb, dtype=torch.uint8, device=dev)
-                module._tws_key = key
+            scratch = torch.empty(4 * h2 * 6, dtype=torch.float32, device=dev)
+            packed = module._train.packed(dev, (lib.opnet_train_packed_weights_bytes, h1, h2), lambda buf, n: _lib.check(
+                lib.opnet_mlp_train_pack_weights_f32(*(w.data_ptr() for w in weights), buf.data_ptr(), n, scratch.data_ptr(),
+                                                     h1, h2, stream), "opnet_mlp_train_pack_weights_f32"), zero=True)
+            tws = module._train.history_for(B, T, dev, (lib.opnet_train_workspace_bytes, B, T, h1, h2))
             y = torch.empty((B, T, 4), dtype=torch.float32, device=dev)
             logits = torch.empty((B, 15, T), dtype=torch.float32, device=dev)
-            rc = lib.opnet_mlp_train_forward_f32(boxes.data_ptr(), module._tpacked.data_ptr(), y.data_ptr(),
-                                                 logits.data_ptr(), module._tws.data_ptr(), module._tws.numel(),
-                                                 B, T, h1, h2, stream)
+            rc = lib.opnet_mlp_train_forward_f32(boxes.data_ptr(), packed.data_ptr(), y.data_ptr(), logits.data_ptr(),
+                                                 tws.data_ptr(), tws.numel(), B, T, h1, h2, stream)
             _lib.check(rc, "opnet_mlp_train_forward_f32")
         module._train_gen += 1
         ctx.module, ctx.gen, ctx.shape = module, module._train_gen, (B, T)
@@ -207,8 +184,8 @@ class _OPNetMlpTrainFunction(torch.autograd.Function):
         g_ih1, g_hh1, g_sel, _, g_out = [torch.empty(s, dtype=torch.float32, device=dev) for s in ctx.wshapes]
         g_hid4 = torch.empty((4 * module._h2, 6), dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
-            rc = lib.opnet_mlp_train_backward_f32(grad_y.data_ptr(), module._tpacked.data_ptr(),
-                                                  module._tws.data_ptr(), module._tws.numel(), g_ih1.data_ptr(),
+            rc = lib.opnet_mlp_train_backward_f32(grad_y.data_ptr(), module._train.image.data_ptr(),
+                                                  module._train.history.data_ptr(), module._train.history.numel(), g_ih1.data_ptr(),
                                                   g_hh1.data_ptr(), g_sel.data_ptr(), g_hid4.data_ptr(),
                                                   g_out.data_ptr(), B, T, module._h1, module._h2, _stream_ptr(dev))
         _lib.check(rc, "opnet_mlp_train_backward_f32")
@@ -233,23 +210,21 @@ class OPNet(AbstractCaterModel):
         self.video_LSTM = LSTMWeights(self.bb_in_dim, h2)
         self.prediction_layer = LinearWeight(h2, self.bb_out_dim)
         self._h1, self._h2 = h1, h2
-        self._packed: Dict[int, Tuple[tuple, torch.Tensor]] = {}      # per stream: (weights key, packed image)
+        self._packed = PackedImages(8, "OPNet")
         self._plans: Dict[Tuple[int, int, int, int], Tuple[int, torch.Tensor]] = {}
         self._retired = []
-        self._tpacked = None     # training: inference tiles + transposed tiles
-        self._tws = None         # training workspace (one forward's history)
-        self._tws_key = None
+        self._train = TrainingBuffers()     # training: inference tiles + transposed tiles, one forward's history
         self._train_gen = 0
         self.use_graph = os.environ.get("OPNET_HIP_EAGER", "0") != "1"
         # per-XCD persistent forward (include/opnet_hip.h): "auto" = batches of at least XCD_MIN_BATCH clips at the
         # reference sizes; "1" / "0" force it on / off
         self.use_xcd = os.environ.get("OPNET_XCD", "auto")
-        self._xws: Dict[Tuple[int, int, int, int], torch.Tensor] = {}
+        self._xws = Workspaces(8)
         self._xcd_ok = None
         # one small request (up to XCD4_MAX_BATCH clips) as one persistent launch of 4-clip groups: "auto" / "1" / "0"
         self.use_xcd4 = os.environ.get("OPNET_XCD4", "auto")
-        self._x4packed: Dict[int, Tuple[tuple, torch.Tensor]] = {}     # per stream: (weights key, packed image)
-        self._x4ws: Dict[Tuple[int, int, int, int], torch.Tensor] = {}
+        self._x4packed = PackedImages(4, "OPNet")
+        self._x4ws = Workspaces(8)
         self._monitor = LaunchMonitor()      # abort words of the persistent launches (launch_monitor.py)
         self._train_aborted = False
 
@@ -275,11 +250,11 @@ class OPNet(AbstractCaterModel):
     def launch_guard(self):
         """the abort word (a 1-element int32 view of the current training workspace) that the persistent launches of a
         training step raise; None: no such launches for this shape - FusedAdam's guard"""
-        if self._tws is None or self._tws_key is None:
+        if self._train.history is None:
             return None
-        B, T, _ = self._tws_key
+        B, T, _ = self._train.key
         off = _lib.load().opnet_train_status_offset(B, T, self._h1, self._h2)
-        return None if off == _lib.NO_OFFSET else self._tws[off:off + 4].view(torch.int32)
+        return None if off == _lib.NO_OFFSET else self._train.history[off:off + 4].view(torch.int32)
 
     def _redo_on_chain(self, boxes: torch.Tensor, y: torch.Tensor, logits: torch.Tensor) -> None:
         with torch.no_grad(), torch.cuda.device(boxes.device):
@@ -294,35 +269,14 @@ class OPNet(AbstractCaterModel):
                 self.video_LSTM.weight_hh_l0, self.prediction_layer.weight)
 
     def _packed_weights(self, device: torch.device) -> torch.Tensor:
-        """the packed image for launches on the CURRENT stream.  One image per stream (at most 8): forwards of this module
-        may be in flight on several streams, and a re-pack after a weight update must not rewrite an image that another
-        stream's earlier launches are still reading - a pack and the launches that read it are always ordered by their
-        own stream (the 4-clip form keeps its images the same way)."""
+        """the packed image for launches on the CURRENT stream (one per stream: _device_cache.py)"""
         lib = _lib.load()
         ws = self._weights()
         stream = _stream_ptr(device)
-        key = tuple((w.data_ptr(), w._version) for w in ws) + (str(device),)
-        entry = self._packed.get(stream)
-        if entry is None or entry[0] != key:
-            for w in ws:
-                if w.device != device or w.dtype != torch.float32 or not w.is_contiguous():
-                    raise RuntimeError("OPNet parameters must be contiguous fp32 on the input's device "
-                                       "(call model.to(device) first)")
-            nbytes = lib.opnet_packed_weights_bytes(self._h1, self._h2)
-            if nbytes == 0:
-                _lib.check(-2, "opnet_packed_weights_bytes")
-            if entry is None or entry[1].device != device:
-                if len(self._packed) >= 8:
-                    # (the evicted image may still be read by launches on ITS stream: the caching allocator hands a block
-                    # back to the stream it was allocated on, so whatever reuses it is ordered behind them)
-                    self._packed.pop(next(iter(self._packed)))
-                buf = torch.empty(nbytes // 4, dtype=torch.float32, device=device)
-            else:
-                buf = entry[1]
-            rc = lib.opnet_pack_weights_f32(*(w.data_ptr() for w in ws), buf.data_ptr(), nbytes, self._h1, self._h2, stream)
-            _lib.check(rc, "opnet_pack_weights_f32")
-            self._packed[stream] = (key, buf)
-        return self._packed[stream][1]
+        return self._packed.get(stream, ws, device, (lib.opnet_packed_weights_bytes, self._h1, self._h2),
+                                lambda buf, n: _lib.check(lib.opnet_pack_weights_f32(
+                                    *(w.data_ptr() for w in ws), buf.data_ptr(), n, self._h1, self._h2, stream),
+                                    "opnet_pack_weights_f32"))
 
     XCD_MIN_BATCH = 64       # measured: 38.3 k clips/s against 37.4 k through the launch chain at 64 clips, 74 k against 49 k at 128
     MAX_PLANS = 16           # (shape, device, stream) launch plans kept alive
@@ -353,38 +307,11 @@ class OPNet(AbstractCaterModel):
         lib = _lib.load()
         B, T, dev = int(boxes.shape[0]), int(boxes.shape[1]), boxes.device
         ws_ = self._weights()
-        key = tuple((w.data_ptr(), w._version) for w in ws_) + (str(dev),)
-        # one packed image per stream (a re-pack on one stream must not rewrite what another stream's launch is reading)
-        entry = self._x4packed.get(stream) if isinstance(self._x4packed, dict) else None
-        if entry is None or entry[0] != key:
-            for w in ws_:
-                if w.device != dev or w.dtype != torch.float32 or not w.is_contiguous():
-                    raise RuntimeError("OPNet parameters must be contiguous fp32 on the input's device "
-                                       "(call model.to(device) first)")
-            nbytes = lib.opnet_xcd4_packed_weights_bytes(self._h1, self._h2)
-            if nbytes == 0:
-                _lib.check(-2, "opnet_xcd4_packed_weights_bytes")
-            if not isinstance(self._x4packed, dict):
-                self._x4packed = {}
-            if entry is None or entry[1].device != dev:
-                if len(self._x4packed) >= 4:
-                    self._x4packed.pop(next(iter(self._x4packed)))
-                buf = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
-            else:
-                buf = entry[1]
-            _lib.check(lib.opnet_xcd4_pack_weights_f32(*(w.data_ptr() for w in ws_), buf.data_ptr(), nbytes,
-                                                       self._h1, self._h2, stream), "opnet_xcd4_pack_weights_f32")
-            self._x4packed[stream] = (key, buf)
-        x4packed = self._x4packed[stream][1]
-        wkey = (B, T, dev.index if dev.index is not None else torch.cuda.current_device(), stream)
-        if wkey not in self._x4ws:
-            nbytes = lib.opnet_xcd4_workspace_bytes(B, T, self._h1, self._h2)
-            if nbytes == 0:
-                _lib.check(-2, "opnet_xcd4_workspace_bytes")
-            if len(self._x4ws) >= 8:
-                self._x4ws.pop(next(iter(self._x4ws)))
-            self._x4ws[wkey] = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        ws = self._x4ws[wkey]
+        x4packed = self._x4packed.get(
+            stream, ws_, dev, (lib.opnet_xcd4_packed_weights_bytes, self._h1, self._h2), lambda buf, n: _lib.check(
+                lib.opnet_xcd4_pack_weights_f32(*(w.data_ptr() for w in ws_), buf.data_ptr(), n, self._h1, self._h2, stream),
+                "opnet_xcd4_pack_weights_f32"))
+        ws = self._x4ws.get(stream, (B, T), dev, (lib.opnet_xcd4_workspace_bytes, B, T, self._h1, self._h2))
         y = torch.empty((B, T, 4), dtype=torch.float32, device=dev)
         logits = torch.empty((B, 15, T), dtype=torch.float32, device=dev)
         _lib.check(lib.opnet_xcd4_forward_f32(boxes.data_ptr(), x4packed.data_ptr(), y.data_ptr(), logits.data_ptr(),
@@ -405,20 +332,7 @@ class OPNet(AbstractCaterModel):
             step //= 2                  # very long clips: the history of a full launch would exceed one buffer descriptor
         for lo in range(0, B, step):
             n = min(step, B - lo)
-            # one workspace per (shape, device, stream), like the launch plans: forwards enqueued on different streams
-            # must not share a history buffer
-            key = (n, T, dev.index if dev.index is not None else torch.cuda.current_device(), stream)
-            if key not in self._xws:
-                nbytes = lib.opnet_xcd_workspace_bytes(n, T, self._h1, self._h2)
-                if nbytes == 0:
-                    _lib.check(-2, "opnet_xcd_workspace_bytes")
-                if len(self._xws) >= 8:
-                    # dropped at once, unlike the chain's plans (a hipGraph must be destroyed by hand, a tensor must not):
-                    # the key holds the stream, the buffer was allocated on it, and the caching allocator only hands a block
-                    # back to its own stream - whatever reuses it runs behind the launch that may still be using it
-                    self._xws.pop(next(iter(self._xws)))
-                self._xws[key] = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-            ws = self._xws[key]
+            ws = self._xws.get(stream, (n, T), dev, (lib.opnet_xcd_workspace_bytes, n, T, self._h1, self._h2))
             rc = lib.opnet_xcd_forward_f32(boxes[lo:lo + n].data_ptr(), packed.data_ptr(), y[lo:lo + n].data_ptr(),
                                            logits[lo:lo + n].data_ptr(), ws.data_ptr(), ws.numel(), n, T,
                                            self._h1, self._h2, stream)
@@ -445,15 +359,9 @@ class OPNet(AbstractCaterModel):
         with torch.cuda.device(dev):
             packed = self._packed_weights(dev)
             stream = _stream_ptr(dev)
-            nbytes = lib.opnet_xcd_workspace_bytes(B, T, self._h1, self._h2)
-            if nbytes == 0:     # a history beyond one buffer descriptor: the chunked path
-                return self(torch.cat(reqs, dim=0))
-            key = (B, T, dev.index if dev.index is not None else torch.cuda.current_device(), stream)
-            if key not in self._xws:
-                if len(self._xws) >= 8:
-                    self._xws.pop(next(iter(self._xws)))
-                self._xws[key] = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-            ws = self._xws[key]
+            if lib.opnet_xcd_workspace_bytes(B, T, self._h1, self._h2) == 0:
+                return self(torch.cat(reqs, dim=0))     # a history beyond one buffer descriptor: the chunked path
+            ws = self._xws.get(stream, (B, T), dev, (lib.opnet_xcd_workspace_bytes, B, T, self._h1, self._h2))
             y = torch.empty((B, T, 4), dtype=torch.float32, device=dev)
             logits = torch.empty((B, 15, T), dtype=torch.float32, device=dev)
             n = len(reqs)
@@ -480,9 +388,7 @@ class OPNet(AbstractCaterModel):
         boxes = boxes.contiguous().float()
         if torch.is_grad_enabled() and any(w.requires_grad for w in self._weights()):
             ws = self._weights()
-            for w in ws:
-                if w.device != boxes.device or w.dtype != torch.float32 or not w.is_contiguous():
-                    raise RuntimeError("OPNet parameters must be contiguous fp32 on the input's device")
+            check_weights(ws, boxes.device, "OPNet")
             return _OPNetTrainFunction.apply(self, boxes, *ws)
         B, T = int(boxes.shape[0]), int(boxes.shape[1])
         dev = boxes.device
@@ -575,27 +481,13 @@ class _StackTrainFunction(torch.autograd.Function):
         L, KX, H = runner.L, runner.KX, runner.H
         B, T, dev = int(x.shape[0]), int(x.shape[1]), x.device
         stream = _stream_ptr(dev)
-        nbytes = lib.opseq_lstm_stack_train_packed_bytes(L, KX, H)
-        if nbytes == 0:
-            _lib.check(-2, "opseq_lstm_stack_train_packed_bytes")
-        if runner.tpacked is None or runner.tpacked.device != dev:
-            runner.tpacked = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
-        arr = _lib.c_void_p * L
-        ih = arr(*[w.data_ptr() for w in weights[:L]])
-        hh = arr(*[w.data_ptr() for w in weights[L:2 * L]])
-        _lib.check(lib.opseq_lstm_stack_train_pack_weights_f32(ih, hh, weights[2 * L].data_ptr(), runner.tpacked.data_ptr(),
-                                                               nbytes, L, KX, H, stream), "opseq_lstm_stack_train_pack_weights_f32")
-        key = (B, T, str(dev))
-        if runner.tws_key != key:
-            wsb = lib.opseq_lstm_stack_train_workspace_bytes(B, T, L, KX, H)
-            if wsb == 0:
-                _lib.check(-2, "opseq_lstm_stack_train_workspace_bytes")
-            runner.tws = None
-            runner.tws = torch.empty(wsb, dtype=torch.uint8, device=dev)
-            runner.tws_key = key
+        packed = runner.train.packed(dev, (lib.opseq_lstm_stack_train_packed_bytes, L, KX, H), lambda buf, n: _lib.check(
+            lib.opseq_lstm_stack_train_pack_weights_f32(*runner._layer_ptrs(weights), weights[2 * L].data_ptr(), buf.data_ptr(), n,
+                                                        L, KX, H, stream), "opseq_lstm_stack_train_pack_weights_f32"))
+        tws = runner.train.history_for(B, T, dev, (lib.opseq_lstm_stack_train_workspace_bytes, B, T, L, KX, H))
         y = torch.empty((B, T, 4), dtype=torch.float32, device=dev)
-        _lib.check(lib.opseq_lstm_stack_train_forward_f32(x.data_ptr(), runner.tpacked.data_ptr(), y.data_ptr(),
-                                                          runner.tws.data_ptr(), runner.tws.numel(), B, T, L, KX, H, stream),
+        _lib.check(lib.opseq_lstm_stack_train_forward_f32(x.data_ptr(), packed.data_ptr(), y.data_ptr(), tws.data_ptr(),
+                                                          tws.numel(), B, T, L, KX, H, stream),
                    "opseq_lstm_stack_train_forward_f32")
         runner.train_gen += 1
         ctx.runner, ctx.gen, ctx.shape = runner, runner.train_gen, (B, T)
@@ -604,7 +496,7 @@ class _StackTrainFunction(torch.autograd.Function):
         # the persistent training forward (H = 512 stacks): its abort words are mirrored to the host behind the launch
         off = lib.opseq_lstm_stack_train_status_offset(B, T, L, KX, H)
         if off != _lib.NO_OFFSET and lib.opseq_xcd_supported(L, KX, H):
-            runner._monitor.watch(runner.tws, off, runner._note_training_abort, "seqx_forward (training)")
+            runner._monitor.watch(tws, off, runner._note_training_abort, "seqx_forward (training)")
         return y
 
     @staticmethod
@@ -619,12 +511,11 @@ class _StackTrainFunction(torch.autograd.Function):
         grad_y = grad_y.contiguous().float()
         grads = [torch.empty(s, dtype=torch.float32, device=dev) for s in ctx.wshapes]
         dx = torch.empty((B, T, KX), dtype=torch.float32, device=dev) if ctx.need_dx else None
-        arr = _lib.c_void_p * L
-        gih = arr(*[g.data_ptr() for g in grads[:L]])
-        ghh = arr(*[g.data_ptr() for g in grads[L:2 * L]])
+        gih, ghh = runner._layer_ptrs(grads)
+        tb = runner.train
         with torch.cuda.device(dev):
-            rc = lib.opseq_lstm_stack_train_backward_f32(grad_y.data_ptr(), runner.tpacked.data_ptr(), runner.tws.data_ptr(),
-                                                         runner.tws.numel(), gih, ghh, grads[2 * L].data_ptr(),
+            rc = lib.opseq_lstm_stack_train_backward_f32(grad_y.data_ptr(), tb.image.data_ptr(), tb.history.data_ptr(),
+                                                         tb.history.numel(), gih, ghh, grads[2 * L].data_ptr(),
                                                          None if dx is None else dx.data_ptr(), B, T, L, KX, H,
                                                          _stream_ptr(dev))
         _lib.check(rc, "opseq_lstm_stack_train_backward_f32")
@@ -633,7 +524,7 @@ class _StackTrainFunction(torch.autograd.Function):
         off = lib.opseq_lstm_stack_train_status_offset(B, T, L, KX, H)
         if off != _lib.NO_OFFSET and lib.opseq_xcd_supported(L, KX, H):
             with torch.cuda.device(dev):
-                runner._monitor.watch(runner.tws, off, runner._note_training_abort, "seqx_backward (training)")
+                runner._monitor.watch(tb.history, off, runner._note_training_abort, "seqx_backward (training)")
         return (None, dx) + tuple(grads)
 
 
@@ -668,25 +559,20 @@ class _SlotEmbedFunction(torch.autograd.Function):
         return None, dW, None
 
 
-def _weights_key(ws, dev):
-    return tuple((w.data_ptr(), w._version) for w in ws) + (str(dev),)
-
-
 class _LstmStackRunner:
     """Packs L stacked LSTM layers + head once per weight version and runs opseq_lstm_stack_forward_f32."""
 
     def __init__(self, layers: int, kx: int, hidden: int):
         self.L, self.KX, self.H = layers, kx, hidden
-        self.packed = None
-        self.key = None
-        self.ws = {}
-        self.tpacked, self.tws, self.tws_key, self.train_gen = None, None, None, 0
+        self._cpacked = PackedImages(4, "LSTM stack")        # the launch chain's image
+        # one shape per stream at a time: the C side caches a hipGraph per workspace, so a new buffer is a new graph
+        self._cws = Workspaces(4, one_per_stream=True)
+        self.train, self.train_gen = TrainingBuffers(), 0
         # the whole stack as ONE persistent launch (csrc/seq_xcd_kernels.hip): "auto" = whenever the library supports the
         # shape on this device (H = 512; the reference's three stacked reasoners) and the batch fits one launch; "0" = never
         self.use_xcd = os.environ.get("OPSEQ_XCD", "auto")
-        self._xpacked: Dict[int, Tuple[tuple, torch.Tensor]] = {}     # per stream: (weights key, register image)
-        self._cpacked: Dict[int, Tuple[tuple, torch.Tensor]] = {}     # per stream: (weights key, the launch chain's packed image)
-        self._xws: Dict[tuple, torch.Tensor] = {}
+        self._xpacked = PackedImages(4, "LSTM stack")        # the register image
+        self._xws = Workspaces(4)
         self._monitor = LaunchMonitor()
         self.xcd_launches = 0            # statistics: forwards that ran as one persistent launch
         # ... and its throughput form (csrc/seq_xcdt_kernels.hip): "auto" = batches of at least XCDT_MIN_BATCH clips, "1" = every
@@ -695,8 +581,8 @@ class _LstmStackRunner:
         # the first batch the 4-clip form needs one more round for (it carries 32 clips a round with one layer, 16 with two): measured
         # (tools/xcdt_threshold_probe.py) 65 clips 1.43 -> 1.20 ms, two layers 33 clips 3.21 -> 3.03 ms; at 64 / 32 the 4-clip form wins
         self.XCDT_MIN_BATCH = int(os.environ.get("OPSEQ_XCDT_MIN_BATCH", 65 if layers == 1 else 33))
-        self._tpacked: Dict[int, Tuple[tuple, torch.Tensor]] = {}
-        self._tws: Dict[tuple, torch.Tensor] = {}
+        self._tpacked = PackedImages(4, "LSTM stack")        # the throughput form's image
+        self._tws = Workspaces(4)
         self.xcdt_launches = 0
 
     def _note_training_abort(self) -> None:
@@ -712,11 +598,21 @@ class _LstmStackRunner:
         return bad
 
     def launch_guard(self):
-        if self.tws is None or self.tws_key is None:
+        if self.train.history is None:
             return None
-        B, T, _ = self.tws_key
+        B, T, _ = self.train.key
         off = _lib.load().opseq_lstm_stack_train_status_offset(B, T, self.L, self.KX, self.H)
-        return None if off == _lib.NO_OFFSET else self.tws[off:off + 4].view(torch.int32)
+        return None if off == _lib.NO_OFFSET else self.train.history[off:off + 4].view(torch.int32)
+
+    def weights(self, lstm: "LSTMWeights", head: "LinearWeight") -> list:
+        """[w_ih_0..L-1, w_hh_0..L-1, head]: the order every pack and training call of the stack takes"""
+        return [getattr(lstm, f"weight_ih_l{l}") for l in range(self.L)] + \
+               [getattr(lstm, f"weight_hh_l{l}") for l in range(self.L)] + [head.weight]
+
+    def _layer_ptrs(self, ws_list):
+        """the C arrays of the L input and L recurrent matrices of ws_list"""
+        arr = _lib.c_void_p * self.L
+        return arr(*[w.data_ptr() for w in ws_list[:self.L]]), arr(*[w.data_ptr() for w in ws_list[self.L:2 * self.L]])
 
     def _wants_xcd(self, B: int, T: Optional[int] = None) -> bool:
         """the persistent launch takes (B, T) when the shape is supported on this device, the batch fits one launch and -
@@ -734,37 +630,11 @@ class _LstmStackRunner:
         dev = x.device
         B, T = int(x.shape[0]), int(x.shape[1])
         stream = _stream_ptr(dev)
-        key = _weights_key(ws_list, dev)
-        entry = self._xpacked.get(stream)
-        if entry is None or entry[0] != key:
-            for w in ws_list:
-                if w.device != dev or w.dtype != torch.float32 or not w.is_contiguous():
-                    raise RuntimeError("parameters must be contiguous fp32 on the input's device")
-            nbytes = lib.opseq_xcd_packed_bytes(self.L, self.KX, self.H)
-            if nbytes == 0:
-                _lib.check(-2, "opseq_xcd_packed_bytes")
-            if entry is None or entry[1].device != dev:
-                if len(self._xpacked) >= 4:
-                    self._xpacked.pop(next(iter(self._xpacked)))
-                buf = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
-            else:
-                buf = entry[1]
-            arr = _lib.c_void_p * self.L
-            ih = arr(*[w.data_ptr() for w in ws_list[:self.L]])
-            hh = arr(*[w.data_ptr() for w in ws_list[self.L:2 * self.L]])
-            _lib.check(lib.opseq_xcd_pack_weights_f32(ih, hh, buf.data_ptr(), nbytes, self.L, self.KX, self.H, stream),
-                       "opseq_xcd_pack_weights_f32")
-            self._xpacked[stream] = (key, buf)
-        packed = self._xpacked[stream][1]
-        wkey = (B, T, str(dev), stream)
-        if wkey not in self._xws:
-            nb = lib.opseq_xcd_workspace_bytes(B, T, self.L, self.KX, self.H)
-            if nb == 0:
-                _lib.check(-2, "opseq_xcd_workspace_bytes")
-            if len(self._xws) >= 4:
-                self._xws.pop(next(iter(self._xws)))      # (stream-keyed: see OPNet._forward_xcd on dropping it at once)
-            self._xws[wkey] = torch.empty(nb, dtype=torch.uint8, device=dev)
-        ws = self._xws[wkey]
+        packed = self._xpacked.get(stream, ws_list, dev, (lib.opseq_xcd_packed_bytes, self.L, self.KX, self.H),
+                                   lambda buf, n: _lib.check(lib.opseq_xcd_pack_weights_f32(
+                                       *self._layer_ptrs(ws_list), buf.data_ptr(), n, self.L, self.KX, self.H, stream),
+                                       "opseq_xcd_pack_weights_f32"))
+        ws = self._xws.get(stream, (B, T), dev, (lib.opseq_xcd_workspace_bytes, B, T, self.L, self.KX, self.H))
         y = torch.empty((B, T, 4), dtype=torch.float32, device=dev)
         _lib.check(lib.opseq_xcd_forward_f32(x.data_ptr(), packed.data_ptr(), head.weight.data_ptr(), y.data_ptr(), ws.data_ptr(),
                                              ws.numel(), B, T, self.L, self.KX, self.H, stream), "opseq_xcd_forward_f32")
@@ -778,11 +648,8 @@ class _LstmStackRunner:
         return y
 
     def run_train(self, x: torch.Tensor, lstm: "LSTMWeights", head: "LinearWeight") -> torch.Tensor:
-        ws_list = [getattr(lstm, f"weight_ih_l{l}") for l in range(self.L)] + \
-                  [getattr(lstm, f"weight_hh_l{l}") for l in range(self.L)] + [head.weight]
-        for w in ws_list:
-            if w.device != x.device or w.dtype != torch.float32 or not w.is_contiguous():
-                raise RuntimeError("parameters must be contiguous fp32 on the input's device")
+        ws_list = self.weights(lstm, head)
+        check_weights(ws_list, x.device, "LSTM stack")
         return _StackTrainFunction.apply(self, x.contiguous(), *ws_list)
 
     # Batches from XCDT_MIN_BATCH clips on run the throughput form (16-clip groups, csrc/seq_xcdt_kernels.hip); below, the 4-clip
@@ -806,41 +673,15 @@ class _LstmStackRunner:
         dev = x.device
         B, T = int(x.shape[0]), int(x.shape[1])
         stream = _stream_ptr(dev)
-        key = _weights_key(ws_list, dev)
-        entry = self._tpacked.get(stream)
-        if entry is None or entry[0] != key:
-            for w in ws_list:
-                if w.device != dev or w.dtype != torch.float32 or not w.is_contiguous():
-                    raise RuntimeError("parameters must be contiguous fp32 on the input's device")
-            nbytes = lib.opseq_xcdt_packed_bytes(self.L, self.KX, self.H)
-            if nbytes == 0:
-                _lib.check(-2, "opseq_xcdt_packed_bytes")
-            if entry is None or entry[1].device != dev:
-                if len(self._tpacked) >= 4:
-                    self._tpacked.pop(next(iter(self._tpacked)))
-                buf = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
-            else:
-                buf = entry[1]
-            arr = _lib.c_void_p * self.L
-            ih = arr(*[w.data_ptr() for w in ws_list[:self.L]])
-            hh = arr(*[w.data_ptr() for w in ws_list[self.L:2 * self.L]])
-            _lib.check(lib.opseq_xcdt_pack_weights_f32(ih, hh, buf.data_ptr(), nbytes, self.L, self.KX, self.H, stream),
-                       "opseq_xcdt_pack_weights_f32")
-            self._tpacked[stream] = (key, buf)
-        packed = self._tpacked[stream][1]
+        packed = self._tpacked.get(stream, ws_list, dev, (lib.opseq_xcdt_packed_bytes, self.L, self.KX, self.H),
+                                   lambda buf, n: _lib.check(lib.opseq_xcdt_pack_weights_f32(
+                                       *self._layer_ptrs(ws_list), buf.data_ptr(), n, self.L, self.KX, self.H, stream),
+                                       "opseq_xcdt_pack_weights_f32"))
         step = int(lib.opseq_xcdt_max_batch(T, self.L, self.KX, self.H))
         y = torch.empty((B, T, 4), dtype=torch.float32, device=dev)
         for b0 in range(0, B, step):
             n = min(step, B - b0)
-            wkey = (n, T, str(dev), stream)
-            if wkey not in self._tws:
-                nb = lib.opseq_xcdt_workspace_bytes(n, T, self.L, self.KX, self.H)
-                if nb == 0:
-                    _lib.check(-2, "opseq_xcdt_workspace_bytes")
-                if len(self._tws) >= 4:
-                    self._tws.pop(next(iter(self._tws)))
-                self._tws[wkey] = torch.empty(nb, dtype=torch.uint8, device=dev)
-            ws = self._tws[wkey]
+            ws = self._tws.get(stream, (n, T), dev, (lib.opseq_xcdt_workspace_bytes, n, T, self.L, self.KX, self.H))
             xc, yc = x[b0:b0 + n], y[b0:b0 + n]
             _lib.check(lib.opseq_xcdt_forward_f32(xc.data_ptr(), packed.data_ptr(), head.weight.data_ptr(), yc.data_ptr(), ws.data_ptr(),
                                                   ws.numel(), n, T, self.L, self.KX, self.H, stream), "opseq_xcdt_forward_f32")
@@ -863,8 +704,7 @@ class _LstmStackRunner:
     def run(self, x: torch.Tensor, lstm: "LSTMWeights", head: "LinearWeight", engine: Optional[str] = None) -> torch.Tensor:
         """engine: None = by this batch's shape; a caller that merged independent requests and wants each of them computed as it
         would be alone passes the lone request's engine"""
-        ws_list = [getattr(lstm, f"weight_ih_l{l}") for l in range(self.L)] + \
-                  [getattr(lstm, f"weight_hh_l{l}") for l in range(self.L)] + [head.weight]
+        ws_list = self.weights(lstm, head)
         if engine is None:
             engine = self.engine(int(x.shape[0]), int(x.shape[1]))
         if engine == "t":
@@ -883,31 +723,10 @@ class _LstmStackRunner:
         """the launch chain's packed image (opseq_lstm_stack_pack_weights_f32) of ws_list = [w_ih_0..L-1, w_hh_0..L-1, head]
         for `stream`, re-packed on it whenever a weight changed since the last pack"""
         lib = _lib.load()
-        key = _weights_key(ws_list, dev)
-        # packed image and workspace PER STREAM (as _run_xcd): a server issues a segmented model's passes on two side streams in
-        # turn - a pass on stream B must neither read an image stream A is still packing nor share A's workspace
-        entry = self._cpacked.get(stream)
-        if entry is None or entry[0] != key:
-            for w in ws_list:
-                if w.device != dev or w.dtype != torch.float32 or not w.is_contiguous():
-                    raise RuntimeError("parameters must be contiguous fp32 on the input's device")
-            nbytes = lib.opseq_lstm_stack_packed_bytes(self.L, self.KX, self.H)
-            if nbytes == 0:
-                _lib.check(-2, "opseq_lstm_stack_packed_bytes")
-            if entry is None or entry[1].device != dev:
-                if len(self._cpacked) >= 4:
-                    self._cpacked.pop(next(iter(self._cpacked)))
-                buf = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
-            else:
-                buf = entry[1]
-            arr = _lib.c_void_p * self.L
-            ih = arr(*[w.data_ptr() for w in ws_list[:self.L]])
-            hh = arr(*[w.data_ptr() for w in ws_list[self.L:2 * self.L]])
-            rc = lib.opseq_lstm_stack_pack_weights_f32(ih, hh, ws_list[2 * self.L].data_ptr(), buf.data_ptr(), nbytes,
-                                                       self.L, self.KX, self.H, stream)
-            _lib.check(rc, "opseq_lstm_stack_pack_weights_f32")
-            self._cpacked[stream] = (key, buf)
-        return self._cpacked[stream][1]
+        return self._cpacked.get(stream, ws_list, dev, (lib.opseq_lstm_stack_packed_bytes, self.L, self.KX, self.H),
+                                 lambda buf, n: _lib.check(lib.opseq_lstm_stack_pack_weights_f32(
+                                     *self._layer_ptrs(ws_list), ws_list[2 * self.L].data_ptr(), buf.data_ptr(), n, self.L,
+                                     self.KX, self.H, stream), "opseq_lstm_stack_pack_weights_f32"))
 
     def _run_chain(self, x: torch.Tensor, ws_list, head: "LinearWeight") -> torch.Tensor:
         """one launch per time step (csrc/seq_kernels.hip lstm_stack_step), T + 2 L - 1 launches as one hipGraph"""
@@ -915,23 +734,12 @@ class _LstmStackRunner:
         dev = x.device
         B, T = int(x.shape[0]), int(x.shape[1])
         stream = _stream_ptr(dev)
-        self.packed = self._packed_weights(ws_list, dev, stream)
-        self.key = self._cpacked[stream][0]
-        wkey = (B, T, str(dev), stream)
-        if wkey not in self.ws:
-            nb = lib.opseq_lstm_stack_workspace_bytes(B, T, self.L, self.KX, self.H)
-            if nb == 0:
-                _lib.check(-2, "opseq_lstm_stack_workspace_bytes")
-            # one shape per stream at a time (the cached hipGraph is keyed by the workspace: a new buffer is a new graph)
-            self.ws = {k: v for k, v in self.ws.items() if k[3] != stream}
-            if len(self.ws) >= 4:
-                self.ws.pop(next(iter(self.ws)))
-            self.ws[wkey] = torch.empty(nb, dtype=torch.uint8, device=dev)
-        ws = self.ws[wkey]
+        packed = self._packed_weights(ws_list, dev, stream)
+        ws = self._cws.get(stream, (B, T), dev, (lib.opseq_lstm_stack_workspace_bytes, B, T, self.L, self.KX, self.H))
         y = torch.empty((B, T, 4), dtype=torch.float32, device=dev)
         fwd = lib.opseq_lstm_stack_forward_f32 if os.environ.get("OPNET_HIP_EAGER", "0") == "1" \
             else lib.opseq_lstm_stack_forward_graph_f32
-        rc = fwd(x.data_ptr(), self.packed.data_ptr(), y.data_ptr(), ws.data_ptr(), ws.numel(), B, T, self.L,
+        rc = fwd(x.data_ptr(), packed.data_ptr(), y.data_ptr(), ws.data_ptr(), ws.numel(), B, T, self.L,
                  self.KX, self.H, stream)
         _lib.check(rc, "opseq_lstm_stack_forward_f32")
         return y
@@ -1090,7 +898,7 @@ class TransformerLstm(AbstractCaterModel):
         self.video_LSTM = LSTMWeights(e, h, num_layers=ll)
         self.predictions_layer = LinearWeight(h, self.bb_out_dim)
         self._runner = _LstmStackRunner(ll, e, h)
-        self._ews: Dict[int, torch.Tensor] = {}      # encoder workspace per stream
+        self._ews = Workspaces(4, grow_only=True)     # the encoder's
         self._tscratch = None
         self._calls = 0
         # tests only: {layer: (attention [nhead, S, S], after out_proj [S, E], after ReLU [S, ffn], after linear2 [S, E])} uint8
@@ -1104,9 +912,7 @@ class TransformerLstm(AbstractCaterModel):
         z = _SlotEmbedFunction.apply(x, self.boxes_linear.weight, 1).view(B * T, self._e)
         for li, layer in enumerate(self.attention_encoder.layers):
             ts = layer.tensors()
-            for t_ in ts:
-                if t_.device != x.device or not t_.is_contiguous() or t_.dtype != torch.float32:
-                    raise RuntimeError("parameters must be contiguous fp32 on the input's device")
+            check_weights(ts, x.device, "TransformerLstm")
             seed = (int(self.dropout_seed) + 1000003 * self._calls + 7919 * li) & 0xFFFFFFFFFFFF
             if self._test_dropout_masks is not None:        # tests: this layer's four masks from buffers (the reference's draws)
                 m = self._test_dropout_masks[li]
@@ -1192,20 +998,10 @@ class TransformerLstm(AbstractCaterModel):
             z = torch.empty((St, e), dtype=torch.float32, device=dev)
             rc = lib.opseq_slot_embed_relu_f32(x.data_ptr(), self.boxes_linear.weight.data_ptr(), z.data_ptr(), St, 1, e, stream)
             _lib.check(rc, "opseq_slot_embed_relu_f32")
-            nb = lib.opseq_encoder_workspace_bytes(St, e, self._nhead, self.FFN)
-            if nb == 0:
-                _lib.check(-2, "opseq_encoder_workspace_bytes")
-            # one encoder workspace per stream: a server keeps two passes in flight on two streams (serving.py)
-            ews = self._ews.get(stream)
-            if ews is None or ews.numel() < nb or ews.device != dev:
-                if len(self._ews) >= 4:
-                    self._ews.pop(next(iter(self._ews)))
-                ews = self._ews[stream] = torch.empty(nb, dtype=torch.uint8, device=dev)
+            ews = self._ews.get(stream, (), dev, (lib.opseq_encoder_workspace_bytes, St, e, self._nhead, self.FFN))
             for layer in self.attention_encoder.layers:
                 ts = layer.tensors()
-                for t_ in ts:
-                    if t_.device != dev or not t_.is_contiguous() or t_.dtype != torch.float32:
-                        raise RuntimeError("parameters must be contiguous fp32 on the input's device")
+                check_weights(ts, dev, "TransformerLstm")
                 if n_seg == 1:
                     rc = lib.opseq_encoder_layer_f32(z.data_ptr(), *(t_.data_ptr() for t_ in ts), ews.data_ptr(),
                                                      ews.numel(), S, e, self._nhead, self.FFN, stream)
@@ -1232,52 +1028,41 @@ class OPNetLstmMlp(AbstractCaterModel):
         self.hidden_layer = LinearWeight(self.bb_in_dim, h2)
         self.prediction_layer = LinearWeight(h2, self.bb_out_dim)
         self._h1, self._h2 = h1, h2
-        self._packed, self._key, self._ws = None, None, {}
-        self._tpacked, self._tscratch, self._tws, self._tws_key, self._train_gen = None, None, None, None, 0
+        self._packed = PackedImages(8, "OPNetLstmMlp")
+        self._ws = Workspaces(8)
+        self._train, self._train_gen = TrainingBuffers(), 0
 
     def _weights(self):
         return [self.object_to_track_LSTM.weight_ih_l0, self.object_to_track_LSTM.weight_hh_l0,
                 self.object_to_track_prediction.weight, self.hidden_layer.weight, self.prediction_layer.weight]
 
     def _packed_weights(self, device: torch.device) -> torch.Tensor:
-        """the packed inference image (opnet_mlp_pack_weights_f32), re-packed on the current stream whenever a weight
-        changed since the last pack"""
+        """the packed inference image (opnet_mlp_pack_weights_f32) for launches on the CURRENT stream (one per stream:
+        _device_cache.py)"""
         lib = _lib.load()
         ws_list = self._weights()
-        key = _weights_key(ws_list, device)
-        if self._key != key:
-            nbytes = lib.opnet_packed_weights_bytes(self._h1, self._h2)
-            if nbytes == 0:
-                _lib.check(-2, "opnet_packed_weights_bytes")
-            if self._packed is None or self._packed.device != device:
-                self._packed = torch.zeros(nbytes // 4, dtype=torch.float32, device=device)
-            rc = lib.opnet_mlp_pack_weights_f32(*(w.data_ptr() for w in ws_list), self._packed.data_ptr(), nbytes,
-                                                self._h1, self._h2, _stream_ptr(device))
-            _lib.check(rc, "opnet_mlp_pack_weights_f32")
-            self._key = key
-        return self._packed
+        stream = _stream_ptr(device)
+        return self._packed.get(stream, ws_list, device, (lib.opnet_packed_weights_bytes, self._h1, self._h2),
+                                lambda buf, n: _lib.check(lib.opnet_mlp_pack_weights_f32(
+                                    *(w.data_ptr() for w in ws_list), buf.data_ptr(), n, self._h1, self._h2, stream),
+                                    "opnet_mlp_pack_weights_f32"), zero=True)
 
     def forward(self, boxes: torch.Tensor):
         _check_input(self, boxes, 6)
         lib = _lib.load()
         boxes = boxes.contiguous().float()
         B, T, dev = int(boxes.shape[0]), int(boxes.shape[1]), boxes.device
-        ws_list = self._weights()
         if _wants_grad(self):
-            for w in ws_list:
-                if w.device != dev or w.dtype != torch.float32 or not w.is_contiguous():
-                    raise RuntimeError("OPNetLstmMlp parameters must be contiguous fp32 on the input's device")
+            ws_list = self._weights()
+            check_weights(ws_list, dev, "OPNetLstmMlp")
             return _OPNetMlpTrainFunction.apply(self, boxes, *ws_list)
         with torch.cuda.device(dev):
             stream = _stream_ptr(dev)
-            self._packed_weights(dev)
-            wkey = (B, T, str(dev), stream)
-            if wkey not in self._ws:
-                self._ws = {wkey: torch.empty(lib.opnet_workspace_bytes(B, T, self._h1, self._h2), dtype=torch.uint8, device=dev)}
-            ws = self._ws[wkey]
+            packed = self._packed_weights(dev)
+            ws = self._ws.get(stream, (B, T), dev, (lib.opnet_workspace_bytes, B, T, self._h1, self._h2))
             y = torch.empty((B, T, 4), dtype=torch.float32, device=dev)
             logits = torch.empty((B, 15, T), dtype=torch.float32, device=dev)
-            rc = lib.opnet_mlp_forward_f32(boxes.data_ptr(), self._packed.data_ptr(), y.data_ptr(), logits.data_ptr(),
+            rc = lib.opnet_mlp_forward_f32(boxes.data_ptr(), packed.data_ptr(), y.data_ptr(), logits.data_ptr(),
                                            ws.data_ptr(), ws.numel(), B, T, self._h1, self._h2, stream)
             _lib.check(rc, "opnet_mlp_forward_f32")
         return y, logits

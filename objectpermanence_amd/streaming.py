@@ -26,12 +26,13 @@ TransformerLstm is not streamed: its encoder attends over the whole sequence, so
 """
 from __future__ import annotations
 
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import List, Optional, Sequence
 
 import numpy as np
 import torch
 
 from . import _lib
+from ._device_cache import Workspaces
 from .learned_models import BaselineLstm, NonLinearLstm, OPNet, OPNetLstmMlp, _stream_ptr
 
 
@@ -88,8 +89,6 @@ class _StreamPool:
     """What every stream pool shares: the model's ROCm device, the slot bookkeeping, the state pool (one row of `row`
     floats per slot, zero at open) and the per-(n, k, stream) workspaces."""
 
-    MAX_WORKSPACES = 8       # (n, k, stream) workspaces kept alive, least recently used dropped first
-
     def __init__(self, model, capacity: int):
         slots = StreamSlots(capacity)
         dev = next(model.parameters()).device
@@ -100,16 +99,13 @@ class _StreamPool:
         self.device = dev
         self.slots = slots
         self.capacity = slots.capacity
-        self._ws: Dict[Tuple[int, int, int], torch.Tensor] = {}
+        self._ws = Workspaces(8)
 
     def _alloc_state(self, row: int, what: str) -> None:
         if row == 0:
             _lib.check(-2, what)
         self._row = int(row)
         self.state = torch.zeros((self.capacity, self._row), dtype=torch.float32, device=self.device)
-
-    def _workspace_bytes(self, n: int, k: int) -> int:
-        raise NotImplementedError
 
     # -- slots --------------------------------------------------------------------------------
     @property
@@ -125,19 +121,6 @@ class _StreamPool:
 
     def close(self, ids: Sequence[int]) -> None:
         self.slots.close(ids)
-
-    def _workspace(self, n: int, k: int, stream: int) -> torch.Tensor:
-        # one per (n, k, stream): calls on different streams must not share one.  A dropped workspace may still be read
-        # by launches on its stream; the caching allocator only hands the block back to that stream, behind them.
-        key = (n, k, stream)
-        ws = self._ws.pop(key, None)
-        if ws is None:
-            nbytes = self._workspace_bytes(n, k)
-            while len(self._ws) >= self.MAX_WORKSPACES:
-                self._ws.pop(next(iter(self._ws)))
-            ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-        self._ws[key] = ws          # most recently used at the end
-        return ws
 
 
 class OPNetStreams(_StreamPool):
@@ -157,12 +140,6 @@ class OPNetStreams(_StreamPool):
         super().__init__(model, capacity)
         self.H1, self.H2 = model._h1, model._h2
         self._alloc_state(_lib.load().opnet_stream_state_floats(self.H1, self.H2), "opnet_stream_state_floats")
-
-    def _workspace_bytes(self, n: int, k: int) -> int:
-        nbytes = _lib.load().opnet_stream_workspace_bytes(n, k, self.H1, self.H2)
-        if nbytes == 0:
-            _lib.check(-2, "opnet_stream_workspace_bytes")
-        return nbytes
 
     # -- state --------------------------------------------------------------------------------
     def get_state(self, ids: Sequence[int]):
@@ -223,7 +200,7 @@ class OPNetStreams(_StreamPool):
             boxes = boxes.contiguous().float()
             packed = self.model._packed_weights(self.device)
             stream = _stream_ptr(self.device)
-            ws = self._workspace(n, k, stream)
+            ws = self._ws.get(stream, (n, k), self.device, (lib.opnet_stream_workspace_bytes, n, k, self.H1, self.H2))
             slots = torch.from_numpy(idx.astype(np.int32)).to(self.device)      # one small H2D copy on this stream
             y = torch.empty((n, k, 4), dtype=torch.float32, device=self.device)
             logits = torch.empty((n, 15, k), dtype=torch.float32, device=self.device)
@@ -254,12 +231,6 @@ class LstmStackStreams(_StreamPool):
         self.L, self.KX, self.H = r.L, r.KX, r.H
         self.slots_per_frame, self.features = model.max_objects_in_frame, model.bb_in_dim
         self._alloc_state(_lib.load().opseq_stream_state_floats(self.L, self.H), "opseq_stream_state_floats")
-
-    def _workspace_bytes(self, n: int, k: int) -> int:
-        nbytes = _lib.load().opseq_stream_workspace_bytes(n, k, self.L, self.KX, self.H)
-        if nbytes == 0:
-            _lib.check(-2, "opseq_stream_workspace_bytes")
-        return nbytes
 
     # -- state --------------------------------------------------------------------------------
     def get_state(self, ids: Sequence[int]):
@@ -309,11 +280,8 @@ class LstmStackStreams(_StreamPool):
                 _lib.check(rc, "opseq_slot_embed_relu_f32")
             else:
                 feats = x
-            lstm, head = m.video_LSTM, m.predictions_layer
-            ws_list = [getattr(lstm, f"weight_ih_l{l}") for l in range(self.L)] + \
-                      [getattr(lstm, f"weight_hh_l{l}") for l in range(self.L)] + [head.weight]
-            packed = m._runner._packed_weights(ws_list, self.device, stream)
-            ws = self._workspace(n, k, stream)
+            packed = m._runner._packed_weights(m._runner.weights(m.video_LSTM, m.predictions_layer), self.device, stream)
+            ws = self._ws.get(stream, (n, k), self.device, (lib.opseq_stream_workspace_bytes, n, k, self.L, self.KX, self.H))
             slots = torch.from_numpy(idx.astype(np.int32)).to(self.device)      # one small H2D copy on this stream
             y = torch.empty((n, k, 4), dtype=torch.float32, device=self.device)
             rc = lib.opseq_stream_step_f32(feats.data_ptr(), slots.data_ptr(), self.state.data_ptr(), packed.data_ptr(),

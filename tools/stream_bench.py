@@ -160,9 +160,7 @@ def bench_stack(args):
             slots = torch.tensor(ids, dtype=torch.int32, device=dev)
             y1 = torch.empty((n, 1, 4), device=dev)
             ws = torch.empty(lib.opseq_stream_workspace_bytes(n, 1, L, KX, H), dtype=torch.uint8, device=dev)
-            wl = [getattr(m.video_LSTM, f"weight_ih_l{l}") for l in range(L)] + \
-                 [getattr(m.video_LSTM, f"weight_hh_l{l}") for l in range(L)] + [m.predictions_layer.weight]
-            packed = r._packed_weights(wl, torch.device(dev), stream)
+            packed = r._packed_weights(r.weights(m.video_LSTM, m.predictions_layer), torch.device(dev), stream)
 
             def abi_call():
                 _lib.check(lib.opseq_stream_step_f32(feats.data_ptr(), slots.data_ptr(), streams.state.data_ptr(),
@@ -193,9 +191,7 @@ def bench_input_product(m, dev, rounds=4):
     r = m._runner
     L, KX, H = r.L, r.KX, r.H
     stream = torch.cuda.current_stream().cuda_stream
-    wl = [getattr(m.video_LSTM, f"weight_ih_l{l}") for l in range(L)] + \
-         [getattr(m.video_LSTM, f"weight_hh_l{l}") for l in range(L)] + [m.predictions_layer.weight]
-    packed = r._packed_weights(wl, torch.device(dev), stream)
+    packed = r._packed_weights(r.weights(m.video_LSTM, m.predictions_layer), torch.device(dev), stream)
     out = []
     for n, k in PRODUCT_SHAPES:
         x = torch.rand((n, k, KX), device=dev)
