@@ -301,6 +301,25 @@ int opseq_stream_step_f32(const float *x, const int32_t *slots, float *state, co
  * OPSEQ_STREAM_SKINNY_MAX_ROWS of them), 1 = the skinny kernel, 2 = the tiled GEMM + repack.  Same bits either way. */
 int opseq_stream_input_product_f32(const float *x, const float *packed, float *xg, void *workspace, size_t workspace_bytes,
                                    int n, int k, int L, int KX, int H, int route, void *stream);
+
+/* ---- the per-frame input encoder of the streams: detections -> input rows, on the device (DetectorStreams) ----------------
+ * The detector's padded outputs of n streams x k frames - det_boxes [n][k][md][4] fp32 pixels (16-byte aligned),
+ * det_scores [n][k][md], det_labels [n][k][md] int64, n_det [n][k] valid rows - become out [n][k][15][n_tracks], the input
+ * rows of OPNet (6 tracks) or the stacked reasoners (5), by the reference's per-frame rules (preprocess_perception_main.py
+ * :31-36, datasets.py:288-324; objectpermanence_amd/datasets.py encode_boxes states them for a whole clip):
+ *   k_f = #{r < n_det : score >= score_thresh} and the first k_f rows are kept; coordinates are truncated toward zero;
+ *   a class's rank is its index in the stream's table row (not there: >= 15); slot s holds the first kept row of rank s
+ *   (the last one for the snitch, 140) as [x1,y1,x2,y2] / [320,240,320,240] in fp64 then fp32, 1, (6) cone_mask[class];
+ *   a missing cone slot gets [0,0,0,0,0,1] when s < the frame's largest rank; everything else is zero.
+ * tables [capacity][OPNET_ONLINE_TABLE_INTS] (16-byte aligned): entries 0..14 class ids or -1 (free), entry 15 the mode,
+ * 0 = fixed (never written), 1 = learned (each frame appends its classes not yet in the row, ascending, while entries
+ * remain).  The row of stream i is tables[slots[i]]; the CALLER checks that slots are in [0, capacity) and distinct
+ * (a slot outside the pool is skipped).  Other rows are not touched.  cone_mask [num_classes] uint8: is_cone per class
+ * id.  Two launches, deterministic, no host synchronisation. */
+#define OPNET_ONLINE_TABLE_INTS 16
+int opnet_online_encode_f32(const float *det_boxes, const float *det_scores, const int64_t *det_labels, const int32_t *n_det,
+                            int md, const int32_t *slots, int32_t *tables, int capacity, const uint8_t *cone_mask,
+                            int num_classes, int n, int k, int n_tracks, float score_thresh, float *out, void *stream);
 /* ---- the same stack as ONE persistent launch (csrc/seq_xcd_kernels.hip) --------------------------------------------------
  * Replaces the T + 2L - 1 step launches above for the reference's three stacked reasoners (learned_models.py:99-101,
  * 135-137, 170-171: H = 512; L = 1 with KX = 75, L = 2 with KX = 256 or the hoisted KX = 3840) on a whole MI355X

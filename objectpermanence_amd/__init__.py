@@ -4,3 +4,4 @@ from .learned_models import (AbstractCaterModel, BaselineLstm, NonLinearLstm, OP
 from .models_factory import ModelsFactory  # noqa: F401
 from .optim import FusedAdam, l1_mean  # noqa: F401
 from .streaming import LstmStackStreams, OPNetStreams  # noqa: F401
+from .detector_streams import DetectorStreams  # noqa: F401

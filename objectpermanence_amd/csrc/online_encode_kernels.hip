@@ -1,0 +1,184 @@
+// online_encode_kernels.hip - gfx950 kernels of the per-frame input encoder (opnet_online_encode_f32, DetectorStreams).
+//
+// The detector's padded outputs of n streams x k frames (boxes [n][k][md][4] fp32 pixels, scores [n][k][md], labels
+// [n][k][md] int64, n_det [n][k]) become the reasoners' input rows out [n][k][15][n_tracks], as
+// preprocess_perception_main.py:31-36 + datasets.py:288-324 do frame by frame (objectpermanence_amd/datasets.py
+// encode_boxes restates them for a whole clip):
+//   score cut : k_f = #{r < n_det : score[r] >= thresh}, the first k_f rows are kept (a count, then a prefix);
+//   cast      : every box coordinate truncated toward zero (astype(int));
+//   slots     : a class's rank is its index in the stream's table row (tables[slot][0..14]; not there: rank 15);
+//               slot s holds the first row of rank s in the frame, the LAST one when the class is the snitch (140);
+//   content   : [x1,y1,x2,y2] / [320,240,320,240] in fp64 then fp32, 1, (6 tracks) is_cone(class); a missing slot is
+//               zero, except that a missing cone slot gets [0,0,0,0,0,1] when s < the frame's largest rank.
+//
+// Table modes (entry 15 of a row): 0 fixed, 1 learned.  A learned row is append-only: each frame appends its classes not
+// yet in the row, ascending, while entries remain.  So after frame j every class of frame j is in the row unless it is
+// full, and encoding frame j with the row as it stands after all k frames gives the bits of encoding it with the row as
+// it stood after frame j: opnet_online_learn updates the rows first (one workgroup walks a stream's k frames), then
+// opnet_online_encode encodes every (stream, frame) independently (one wave each).  Both are deterministic.
+#pragma once
+
+#define ONLINE_SLOTS 15
+#define ONLINE_SNITCH 140
+#define ONLINE_MODE_LEARNED 1
+#define ONLINE_LEARN_FRAMES 128       // frames of one learn chunk (their n_det and k_f live in LDS)
+
+struct OnlineArgs {
+    const float *boxes;               // [n][k][md][4]
+    const float *scores;              // [n][k][md]
+    const long long *labels;          // [n][k][md]
+    const int32_t *n_det;             // [n][k]
+    const int32_t *slots;             // [n]
+    int32_t *tables;                  // [capacity][16]
+    const uint8_t *cone;              // [num_classes]
+    float *out;                       // [n][k][15][n_tracks]
+    int md, capacity, num_classes, n, k, n_tracks;
+    float thresh;
+};
+
+// a label's class id as a table entry, or -1 when it can never be one (outside [0, 2^31 - 1))
+__device__ __forceinline__ int online_class(long long label)
+{
+    return (label >= 0 && label < 0x7fffffffLL) ? (int)label : -1;
+}
+
+// n workgroups x 256: workgroup i appends the new classes of stream i's k frames to its learned table row, in frame
+// order, each frame's ascending.  A round finds the smallest (frame, class) over the kept rows of the chunk whose class
+// is not in the row yet: that is the next class the frame-by-frame walk appends.  Rounds end when none is left or the
+// row is full (at most 14 appends over a stream's life: slot 0 is the snitch's from open).
+__global__ void __launch_bounds__(256) opnet_online_learn(const OnlineArgs a)
+{
+    __shared__ int tab[ONLINE_SLOTS];
+    __shared__ int nd[ONLINE_LEARN_FRAMES];
+    __shared__ int kf[ONLINE_LEARN_FRAMES];
+    __shared__ unsigned long long red[4];
+    __shared__ int used_s;
+
+    const int i = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const long slot = a.slots[i];
+    if (slot < 0 || slot >= a.capacity) return;             // the host checks slots; a wild one is skipped, not followed
+    int32_t *row = a.tables + slot * 16;
+    if (row[15] != ONLINE_MODE_LEARNED) return;              // uniform over the workgroup
+    if (tid < ONLINE_SLOTS) tab[tid] = row[tid];
+    if (tid == 0) {
+        int u = 0;
+        while (u < ONLINE_SLOTS && row[u] != -1) ++u;
+        used_s = u;
+    }
+    __syncthreads();
+    int used = used_s;
+    const int md = a.md;
+    for (int f0 = 0; f0 < a.k && used < ONLINE_SLOTS; f0 += ONLINE_LEARN_FRAMES) {
+        const int F = min(ONLINE_LEARN_FRAMES, a.k - f0);
+        const long frame0 = (long)i * a.k + f0;             // first (stream, frame) of the chunk
+        if (tid < F) {
+            nd[tid] = min(max(a.n_det[frame0 + tid], 0), md);
+            kf[tid] = 0;
+        }
+        __syncthreads();
+        const long rows = (long)F * md;
+        for (long q = tid; q < rows; q += 256) {
+            const int f = (int)(q / md), r = (int)(q - (long)f * md);
+            if (r < nd[f] && a.scores[frame0 * md + q] >= a.thresh) atomicAdd(&kf[f], 1);
+        }
+        __syncthreads();
+        while (used < ONLINE_SLOTS) {
+            unsigned long long best = ~0ull;
+            for (long q = tid; q < rows; q += 256) {
+                const int f = (int)(q / md), r = (int)(q - (long)f * md);
+                if (r >= kf[f]) continue;
+                const int c = online_class(a.labels[frame0 * md + q]);
+                if (c < 0) continue;
+                bool known = false;
+#pragma unroll
+                for (int e = 0; e < ONLINE_SLOTS; ++e) known |= tab[e] == c;
+                if (!known) best = min(best, ((unsigned long long)f << 32) | (unsigned)c);
+            }
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) best = min(best, (unsigned long long)__shfl_xor(best, o));
+            if (lane == 0) red[wave] = best;
+            __syncthreads();
+            if (tid == 0) {
+                const unsigned long long m = min(min(red[0], red[1]), min(red[2], red[3]));
+                if (m != ~0ull) tab[used_s++] = (int)(m & 0xffffffffu);
+            }
+            __syncthreads();
+            const int u = used_s;
+            if (u == used) break;                             // nothing new in this chunk
+            used = u;
+        }
+        __syncthreads();                                      // nd / kf are rewritten by the next chunk
+    }
+    if (tid < ONLINE_SLOTS) row[tid] = tab[tid];
+}
+
+// ceil(n*k / 4) workgroups x 256: wave w of workgroup b encodes (stream, frame) item 4b + w.  Lane s < 15 owns slot s.
+__global__ void __launch_bounds__(256) opnet_online_encode(const OnlineArgs a)
+{
+    const int lane = threadIdx.x & 63;
+    const long item = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (item >= (long)a.n * a.k) return;
+    const int i = (int)(item / a.k);
+    const long slot = a.slots[i];
+    if (slot < 0 || slot >= a.capacity) return;
+    const int32_t *row = a.tables + slot * 16;
+    int tab[ONLINE_SLOTS];
+#pragma unroll
+    for (int e = 0; e < ONLINE_SLOTS; ++e) tab[e] = row[e];
+    const int md = a.md;
+    const long base = item * md;
+    const int nd = min(max(a.n_det[item], 0), md);
+
+    // score cut: a count over the first n_det rows, then a prefix
+    int kept = 0;
+    for (int r0 = 0; r0 < nd; r0 += 64) {
+        const int r = r0 + lane;
+        kept += __popcll(__ballot(r < nd && a.scores[base + r] >= a.thresh));
+    }
+
+    // slot picks: per 64-row chunk one ballot per rank; first row (last for the snitch) of rank s -> lane s
+    int pick = -1, max_rank = -1;
+    for (int r0 = 0; r0 < kept; r0 += 64) {
+        const int r = r0 + lane;
+        int rank = -1;
+        if (r < kept) {
+            const int c = online_class(a.labels[base + r]);
+            rank = ONLINE_SLOTS;
+#pragma unroll
+            for (int e = ONLINE_SLOTS - 1; e >= 0; --e)
+                if (c >= 0 && tab[e] == c) rank = e;
+        }
+        if (__ballot(rank == ONLINE_SLOTS)) max_rank = ONLINE_SLOTS;
+#pragma unroll
+        for (int s = 0; s < ONLINE_SLOTS; ++s) {
+            const unsigned long long m = __ballot(rank == s);
+            if (m) {
+                max_rank = max(max_rank, s);
+                if (lane == s) {
+                    if (tab[s] == ONLINE_SNITCH) pick = r0 + 63 - __clzll(m);
+                    else if (pick < 0) pick = r0 + __ffsll((long long)m) - 1;
+                }
+            }
+        }
+    }
+
+    if (lane >= ONLINE_SLOTS) return;
+    const int s = lane;
+    const int c = tab[s];
+    const float cone = (c >= 0 && c < a.num_classes && a.cone[c]) ? 1.f : 0.f;
+    float v[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    if (pick >= 0) {
+        const float4 b = *(const float4 *)(a.boxes + (base + pick) * 4);
+        // astype(int) makes an integer, so a coordinate in (-1, 0) becomes +0: trunc gives -0, and + 0.0 turns it into +0
+        v[0] = (float)((trunc((double)b.x) + 0.0) / 320.0);
+        v[1] = (float)((trunc((double)b.y) + 0.0) / 240.0);
+        v[2] = (float)((trunc((double)b.z) + 0.0) / 320.0);
+        v[3] = (float)((trunc((double)b.w) + 0.0) / 240.0);
+        v[4] = 1.f;
+        v[5] = cone;
+    } else if (s < max_rank) {
+        v[5] = cone;
+    }
+    float *o = a.out + (item * ONLINE_SLOTS + s) * a.n_tracks;
+    for (int t = 0; t < a.n_tracks; ++t) o[t] = v[t];
+}

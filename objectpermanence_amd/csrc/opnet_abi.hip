@@ -16,6 +16,7 @@
 #include "attn_train_kernels.hip"
 #include "opnet_stream_kernels.hip"
 #include "seq_stream_kernels.hip"
+#include "online_encode_kernels.hip"
 
 #include <stdarg.h>
 #include <stdlib.h>
@@ -3033,6 +3034,7 @@ extern "C" int opseq_encoder_layer_batched_f32(float *z, const float *in_w, cons
 #include "enc_train_abi.hip"
 #include "opnet_stream_abi.hip"
 #include "seq_stream_abi.hip"
+#include "online_encode_abi.hip"
 
 // ------------------------------------------------------------------------------------------------
 // detector backbone primitives (NHWC fp32)

@@ -339,6 +339,15 @@ class FasterRCNNHeads:
         selection ones (proposals, RoIAlign, detections) - is launched ONCE for all the images of a run that share (resized size,
         original size): the frames of a video do, so a pass is one run (reference detector.py:84 calls the model per frame).
         -> list of padded (boxes [md,4], scores [md], labels [md], n_det [1]) per image"""
+        outs = [None] * int(next(iter(feats.values())).shape[0])
+        for (a, b), (boxes, scores, labels, n_det) in self.forward_runs(feats, image_sizes, padded_size, original_sizes):
+            for i in range(a, b):
+                outs[i] = (boxes[i - a], scores[i - a], labels[i - a], n_det[i - a:i - a + 1])
+        return outs
+
+    def forward_runs(self, feats: "OrderedDict[str, torch.Tensor]", image_sizes, padded_size, original_sizes):
+        """forward_images' work, its results per run: -> list of ((a, b), (boxes [b-a,md,4], scores [b-a,md], labels [b-a,md],
+        n_det [b-a])) for the maximal runs [a, b) of images with one geometry"""
         n = int(next(iter(feats.values())).shape[0])
         head = self.rpn_head(feats)
         maps = list(feats.values())
@@ -358,12 +367,8 @@ class FasterRCNNHeads:
             self.roi_align(maps if whole else [m[a:b] for m in maps], p, count, image_sizes[a], out=pooled[a * r:b * r])
             props.append((p, count))
         cls, reg = self.box_heads(pooled)
-        outs = [None] * n
-        for (a, b), (p, count) in zip(runs, props):
-            boxes, scores, labels, n_det = self.detections(cls[a * r:b * r], reg[a * r:b * r], p, count, image_sizes[a], original_sizes[a])
-            for i in range(a, b):
-                outs[i] = (boxes[i - a], scores[i - a], labels[i - a], n_det[i - a:i - a + 1])
-        return outs
+        return [((a, b), self.detections(cls[a * r:b * r], reg[a * r:b * r], p, count, image_sizes[a], original_sizes[a]))
+                for (a, b), (p, count) in zip(runs, props)]
 
 
 class ResNet50FPNBackbone:
@@ -491,6 +496,19 @@ class CaterObjectDetector(object):
 
     def _enqueue(self, frames, compute_device):
         """everything of one pass enqueued on the current stream; no host sync"""
+        return self._enqueue_with(frames, compute_device, "forward_images")
+
+    def _enqueue_padded(self, frames, compute_device):
+        """one pass (<= MAX_FRAMES_PER_PASS frames of one shape) enqueued on the current stream, its detections left on the
+        device as the batched padded tensors RoIHeads' stage writes: (boxes [p, md, 4] fp32 pixels, scores [p, md] descending,
+        labels [p, md] int64, n_det [p] int32; rows >= n_det zero).  No host sync (DetectorStreams)."""
+        if len(frames) > self.MAX_FRAMES_PER_PASS:
+            raise ValueError(f"at most {self.MAX_FRAMES_PER_PASS} frames per pass")
+        runs = self._enqueue_with(frames, compute_device, "forward_runs")
+        assert len(runs) == 1, "frames of one shape are one run"
+        return runs[0][1]
+
+    def _enqueue_with(self, frames, compute_device, heads_forward: str):
         if self.backbone is None:
             raise RuntimeError("load_model() first")
         if len({f.shape for f in frames}) != 1:
@@ -500,7 +518,7 @@ class CaterObjectDetector(object):
         sizes = [resized_size(h, w, self.min_size, self.max_size) for h, w in hw]
         with torch.cuda.device(x.device):
             feats = self.backbone.forward_nhwc(x)
-            return self.heads.forward_images(feats, sizes, x.shape[1:3], hw)
+            return getattr(self.heads, heads_forward)(feats, sizes, x.shape[1:3], hw)
 
     def _finish(self, outs):
         counts = torch.cat([o[3] for o in outs]).tolist()              # the one host sync of a pass

@@ -194,14 +194,20 @@ class OPNetStreams(_StreamPool):
         n = idx.size
         if boxes.dim() != 4 or boxes.shape[0] != n or boxes.shape[2] != 15 or boxes.shape[3] != 6 or boxes.shape[1] < 1:
             raise ValueError(f"boxes must be [n={n}, k>=1, 15, 6], got {tuple(boxes.shape)}")
-        k = int(boxes.shape[1])
+        with torch.cuda.device(self.device):
+            slots = torch.from_numpy(idx.astype(np.int32)).to(self.device)      # one small H2D copy on this stream
+        return self._step_slots(slots, boxes)
+
+    def _step_slots(self, slots: torch.Tensor, boxes: torch.Tensor):
+        """step with the slot ids already on the device (int32 [n], checked by the caller) and boxes [n, k, 15, 6]
+        checked: no host synchronisation"""
+        n, k = int(boxes.shape[0]), int(boxes.shape[1])
         lib = _lib.load()
         with torch.no_grad(), torch.cuda.device(self.device):
             boxes = boxes.contiguous().float()
             packed = self.model._packed_weights(self.device)
             stream = _stream_ptr(self.device)
             ws = self._ws.get(stream, (n, k), self.device, (lib.opnet_stream_workspace_bytes, n, k, self.H1, self.H2))
-            slots = torch.from_numpy(idx.astype(np.int32)).to(self.device)      # one small H2D copy on this stream
             y = torch.empty((n, k, 4), dtype=torch.float32, device=self.device)
             logits = torch.empty((n, 15, k), dtype=torch.float32, device=self.device)
             rc = lib.opnet_stream_step_f32(boxes.data_ptr(), slots.data_ptr(), self.state.data_ptr(), packed.data_ptr(),
@@ -267,7 +273,15 @@ class LstmStackStreams(_StreamPool):
         S, F = self.slots_per_frame, self.features
         if x.dim() != 4 or x.shape[0] != n or x.shape[2] != S or x.shape[3] != F or x.shape[1] < 1:
             raise ValueError(f"x must be [n={n}, k>=1, {S}, {F}], got {tuple(x.shape)}")
-        k = int(x.shape[1])
+        with torch.cuda.device(self.device):
+            slots = torch.from_numpy(idx.astype(np.int32)).to(self.device)      # one small H2D copy on this stream
+        return self._step_slots(slots, x)
+
+    def _step_slots(self, slots: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
+        """step with the slot ids already on the device (int32 [n], checked by the caller) and x [n, k, 15, 5] checked:
+        no host synchronisation"""
+        n, k = int(x.shape[0]), int(x.shape[1])
+        S = self.slots_per_frame
         m = self.model
         lib = _lib.load()
         with torch.no_grad(), torch.cuda.device(self.device):
@@ -282,7 +296,6 @@ class LstmStackStreams(_StreamPool):
                 feats = x
             packed = m._runner._packed_weights(m._runner.weights(m.video_LSTM, m.predictions_layer), self.device, stream)
             ws = self._ws.get(stream, (n, k), self.device, (lib.opseq_stream_workspace_bytes, n, k, self.L, self.KX, self.H))
-            slots = torch.from_numpy(idx.astype(np.int32)).to(self.device)      # one small H2D copy on this stream
             y = torch.empty((n, k, 4), dtype=torch.float32, device=self.device)
             rc = lib.opseq_stream_step_f32(feats.data_ptr(), slots.data_ptr(), self.state.data_ptr(), packed.data_ptr(),
                                            y.data_ptr(), ws.data_ptr(), ws.numel(), n, k, self.capacity, self.L, self.KX,
