@@ -121,13 +121,16 @@ def non_linear_lstm_forward(x: torch.Tensor, p: Dict[str, torch.Tensor]) -> torc
     return h @ p["predictions_layer.weight"].t()
 
 
-def opnet_lstm_mlp_forward(x: torch.Tensor, p: Dict[str, torch.Tensor]) -> torch.Tensor:
-    """OPNetLstmMlp.forward (learned_models.py:72-89): OPNet's selection stage, then relu(Linear 6->H2) -> Linear"""
+def opnet_lstm_mlp_forward(x: torch.Tensor, p: Dict[str, torch.Tensor], with_logits: bool = False):
+    """OPNetLstmMlp.forward (learned_models.py:72-89): OPNet's selection stage, then relu(Linear 6->H2) -> Linear; with_logits:
+    (y, the selection logits [B, 15, T]) as the model returns them"""
     B, T = x.shape[:2]
     h1 = lstm_seq(x.reshape(B, T, -1), p["object_to_track_LSTM.weight_ih_l0"], p["object_to_track_LSTM.weight_hh_l0"])
-    probs = torch.softmax(h1 @ p["object_to_track_prediction.weight"].t(), dim=-1)
+    logits = h1 @ p["object_to_track_prediction.weight"].t()
+    probs = torch.softmax(logits, dim=-1)
     frames_boxes = torch.einsum("bfot,bfo->bft", x, probs)
-    return torch.relu(frames_boxes @ p["hidden_layer.weight"].t()) @ p["prediction_layer.weight"].t()
+    y = torch.relu(frames_boxes @ p["hidden_layer.weight"].t()) @ p["prediction_layer.weight"].t()
+    return (y, logits.permute(0, 2, 1).contiguous()) if with_logits else y
 
 
 def encoder_layer_forward(z: torch.Tensor, p: Dict[str, torch.Tensor], prefix: str, nhead: int) -> torch.Tensor:
@@ -165,6 +168,33 @@ def transformer_lstm_forward(x: torch.Tensor, p: Dict[str, torch.Tensor], nhead:
         z = encoder_layer_forward(z, p, f"attention_encoder.layers.{li}.", nhead)
         li += 1
     h = z.reshape(B, T, E)
+    l = 0
+    while f"video_LSTM.weight_ih_l{l}" in p:
+        h = lstm_seq(h, p[f"video_LSTM.weight_ih_l{l}"], p[f"video_LSTM.weight_hh_l{l}"])
+        l += 1
+    return h @ p["predictions_layer.weight"].t()
+
+
+def transformer_lstm_segments_forward(x: torch.Tensor, p: Dict[str, torch.Tensor], nhead: int, n_seg: int) -> torch.Tensor:
+    """TransformerLstm.forward_segments: x [n_seg * b, T, 15, 5] holds n_seg independent requests of b clips back to back, and
+    each request's rows of the result are its own transformer_lstm_forward.  The encoder runs per request (attention spans the
+    S = b*T tokens of that request), the stacked LSTM once over all clips (clips are independent there).  Pinned to
+    transformer_lstm_forward of each request (tests/test_siblings_train.py, tests/test_inference_routes_oracle_gpu.py)"""
+    B, T = x.shape[:2]
+    if n_seg <= 0 or B % n_seg:
+        raise ValueError(f"{B} clips do not split into {n_seg} equal requests")
+    z = torch.relu(x[:, :, 0, :] @ p["boxes_linear.weight"].t()).reshape(B * T, -1)
+    E = z.shape[1]
+    S = B * T // n_seg
+    segs = []
+    for s in range(n_seg):
+        zs = z[s * S:(s + 1) * S]
+        li = 0
+        while f"attention_encoder.layers.{li}.linear1.weight" in p:
+            zs = encoder_layer_forward(zs, p, f"attention_encoder.layers.{li}.", nhead)
+            li += 1
+        segs.append(zs)
+    h = torch.cat(segs).reshape(B, T, E)
     l = 0
     while f"video_LSTM.weight_ih_l{l}" in p:
         h = lstm_seq(h, p[f"video_LSTM.weight_ih_l{l}"], p[f"video_LSTM.weight_hh_l{l}"])

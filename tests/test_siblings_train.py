@@ -343,3 +343,25 @@ def test_slot_embed_weight_gradient_with_workspace_matches_torch_and_the_column_
     assert (got[0] - got[2]).abs().max().item() <= 2e-5 * scale
     assert lib.opseq_slot_embed_relu_bwd_ws_f32(xd.data_ptr(), out.data_ptr(), dd.data_ptr(), got[0].data_ptr(), ntok, nslots, F,
                                                 ws.data_ptr(), 16, st) == -3          # OPNET_EWORKSPACE
+
+
+def test_segmented_transformer_port_matches_each_requests_lone_forward():
+    """torch_port.transformer_lstm_segments_forward (the fp64 reference of TransformerLstm.forward_segments, one encoder pass per
+    request, one stack over all clips) gives every request the rows of its own transformer_lstm_forward; the same clips as ONE
+    coupled minibatch give something else (attention spans all S = B*T tokens there)"""
+    import torch
+    cfg = {"boxes_features_dim": 32, "num_attention_heads": 2, "num_attention_layers": 2, "num_lstm_layers": 2,
+           "lstm_hidden_dim": 48}
+    p = {k: torch.tensor(v, dtype=torch.float64) for k, v in PARAMS["transformer_lstm"](cfg).items()}
+    n, b, T = 3, 2, 9
+    x = torch.tensor(synth.boxes5(synth.make_batch(70, n * b, T)[0]), dtype=torch.float64)
+    y = torch_port.transformer_lstm_segments_forward(x, p, 2, n)
+    assert y.shape == (n * b, T, 4)
+    for r in range(n):
+        lone = torch_port.transformer_lstm_forward(x[r * b:(r + 1) * b], p, 2)
+        assert float((y[r * b:(r + 1) * b] - lone).abs().max()) <= 1e-10, r
+    assert float((torch_port.transformer_lstm_segments_forward(x, p, 2, 1) - torch_port.transformer_lstm_forward(x, p, 2)).abs().max()) <= 1e-10
+    coupled = torch_port.transformer_lstm_forward(x, p, 2)
+    assert float((coupled[:b] - y[:b]).abs().max()) > 1e-3
+    with pytest.raises(ValueError):
+        torch_port.transformer_lstm_segments_forward(x, p, 2, 4)

@@ -30,17 +30,21 @@ def _requests(first, n, b, T):
     return [torch.from_numpy(synth.boxes5(synth.make_batch(first + 7 * r, b, T)[0])).cuda() for r in range(n)]
 
 
-# (4, 8, 4, 300): eight coupled requests of four clips (S = 1 200 each)
+# (4, 8, 4, 300): eight coupled requests of four clips (S = 1 200 each); (2, 33, 1, 20): XCDT_MIN_BATCH one-clip requests, which
+# the default pass would run on the throughput form - exact = True keeps the lone request's kernels there
 @pytest.mark.parametrize("heads,n,b,T", [(2, 16, 1, 300), (4, 16, 1, 300), (4, 5, 2, 300), (2, 7, 1, 37), (4, 3, 3, 50), (2, 32, 1, 20),
-                                         (4, 8, 4, 300)])
+                                         (4, 8, 4, 300), (2, 33, 1, 20)])
 def test_every_request_of_a_merged_pass_is_bit_identical_to_its_lone_forward(heads, n, b, T):
     cfg = dict(REAL, num_attention_heads=heads)
     m = _model(cfg)
     reqs = _requests(100, n, b, T)
+    exact = n * b >= m._runner.XCDT_MIN_BATCH
+    assert exact == (n == 33)
     with torch.no_grad():
         alone = [m(r).clone() for r in reqs]
-        merged = m.forward_segments(torch.cat(reqs), n)
+        merged = m.forward_segments(torch.cat(reqs), n, exact=exact)
     torch.cuda.synchronize()
+    assert m.last_pass_engine == "x"
     assert m._runner._monitor.verify() == 0
     assert merged.shape == (n * b, T, 4)
     for r in range(n):
@@ -131,7 +135,7 @@ def test_a_pass_is_cut_where_the_lone_engine_would_change():
         m.forward_segments(torch.cat(reqs), len(reqs), exact=True)
 
 
-@pytest.mark.parametrize("heads,n,b,T", [(2, 70, 1, 40), (4, 40, 2, 30), (2, 130, 1, 12)])
+@pytest.mark.parametrize("heads,n,b,T", [(2, 70, 1, 40), (4, 40, 2, 30), (2, 130, 1, 12), (2, 33, 1, 20)])
 def test_a_large_pass_takes_the_throughput_form_and_agrees_to_rounding(heads, n, b, T):
     """_LstmStackRunner.XCDT_MIN_BATCH clips or more in one pass (exact = False, the default): token-wise products on large tiles, the stacked LSTM on 16-clip
     groups (csrc/seq_xcdt_kernels.hip) - every request agrees with its lone forward to rounding, the pass reproduces itself bit
