@@ -262,6 +262,14 @@ size_t opnet_stream_workspace_bytes(int n, int k, int H1, int H2);   /* 0 on bad
 int opnet_stream_step_f32(const float *boxes, const int32_t *slots, float *state, const float *packed, float *y,
                           float *logits, void *workspace, size_t workspace_bytes, int n, int k, int capacity, int H1,
                           int H2, int mlp, void *stream);
+/* Ragged steps: stream i consumes boxes[i][0 .. lengths[i]) (lengths device int32 [n], 4-byte aligned, not null; the
+ * kernels clamp each to [0, k]); the rest of its row is padding and may hold anything, NaN included.  y / logits of a
+ * valid frame have the bits of the uniform call over the same n streams, padding frames are +0.0, and a stream's pool row
+ * ends with its state after lengths[i] frames (0: unchanged).  Shapes, alignment, launches and the workspace
+ * (opnet_stream_workspace_bytes(n, k, ...)) as the uniform call. */
+int opnet_stream_step_ragged_f32(const float *boxes, const int32_t *slots, const int32_t *lengths, float *state,
+                                 const float *packed, float *y, float *logits, void *workspace, size_t workspace_bytes, int n,
+                                 int k, int capacity, int H1, int H2, int mlp, void *stream);
 
 /* L (1..3) stacked bias-free LSTM layers (input width KX, hidden H each) + Linear H->4:
  *   x [B,T,KX] -> y [B,T,4].  BaselineLstm (:92-118): L=1, KX=75.  NonLinearLstm (:121-151): L=2,
@@ -295,6 +303,12 @@ size_t opseq_stream_state_floats(int L, int H);                                 
 size_t opseq_stream_workspace_bytes(int n, int k, int L, int KX, int H);        /* 0 on bad sizes */
 int opseq_stream_step_f32(const float *x, const int32_t *slots, float *state, const float *packed, float *y, void *workspace,
                           size_t workspace_bytes, int n, int k, int capacity, int L, int KX, int H, void *stream);
+/* Ragged steps, as opnet_stream_step_ragged_f32: stream i consumes x[i][0 .. lengths[i]) (device int32 [n], not null,
+ * clamped to [0, k]); y of a valid frame has the uniform call's bits, padding frames are +0.0, the pool row ends with the
+ * state after lengths[i] frames.  Everything else as opseq_stream_step_f32. */
+int opseq_stream_step_ragged_f32(const float *x, const int32_t *slots, const int32_t *lengths, float *state,
+                                 const float *packed, float *y, void *workspace, size_t workspace_bytes, int n, int k,
+                                 int capacity, int L, int KX, int H, void *stream);
 /* the hoisted layer-0 input product of such a call alone (NonLinearLstm; for measurement and tests):
  * xg [k][ceil(n/32)][H][32][4] = x . W_ih0^T in the step kernel's layout, clips past n zero.  route 0 = as
  * opseq_stream_step_f32 picks it (the skinny kernel computes k * ceil(n/16) * 16 rows; it takes calls of at most
@@ -320,6 +334,12 @@ int opseq_stream_input_product_f32(const float *x, const float *packed, float *x
 int opnet_online_encode_f32(const float *det_boxes, const float *det_scores, const int64_t *det_labels, const int32_t *n_det,
                             int md, const int32_t *slots, int32_t *tables, int capacity, const uint8_t *cone_mask,
                             int num_classes, int n, int k, int n_tracks, float score_thresh, float *out, void *stream);
+/* Ragged calls: frame j of stream i is padding when j >= lengths[i] (device int32 [n], 4-byte aligned, not null, clamped
+ * to [0, k]) and counts as n_det = 0: it appends nothing to a learned row and encodes as zeros. */
+int opnet_online_encode_ragged_f32(const float *det_boxes, const float *det_scores, const int64_t *det_labels,
+                                   const int32_t *n_det, const int32_t *lengths, int md, const int32_t *slots, int32_t *tables,
+                                   int capacity, const uint8_t *cone_mask, int num_classes, int n, int k, int n_tracks,
+                                   float score_thresh, float *out, void *stream);
 /* ---- the same stack as ONE persistent launch (csrc/seq_xcd_kernels.hip) --------------------------------------------------
  * Replaces the T + 2L - 1 step launches above for the reference's three stacked reasoners (learned_models.py:99-101,
  * 135-137, 170-171: H = 512; L = 1 with KX = 75, L = 2 with KX = 256 or the hoisted KX = 3840) on a whole MI355X

@@ -116,6 +116,9 @@ def _declare(lib):
     lib.opnet_stream_step_f32.restype = c_int
     lib.opnet_stream_step_f32.argtypes = [fp, fp, fp, fp, fp, fp, c_void_p, c_size_t, c_int, c_int, c_int, c_int, c_int,
                                           c_int, c_void_p]
+    lib.opnet_stream_step_ragged_f32.restype = c_int
+    lib.opnet_stream_step_ragged_f32.argtypes = [fp, fp, fp, fp, fp, fp, fp, c_void_p, c_size_t, c_int, c_int, c_int, c_int,
+                                                 c_int, c_int, c_void_p]
     lib.opnet_online_encode_f32.restype = c_int
     lib.opnet_online_encode_f32.argtypes = [fp, fp, fp, fp, c_int, fp, fp, c_int, fp, c_int, c_int, c_int, c_int, c_float, fp,
                                             c_void_p]
@@ -144,6 +147,12 @@ def _declare(lib):
     lib.opseq_stream_step_f32.restype = c_int
     lib.opseq_stream_step_f32.argtypes = [fp, fp, fp, fp, fp, c_void_p, c_size_t, c_int, c_int, c_int, c_int, c_int, c_int,
                                           c_void_p]
+    lib.opseq_stream_step_ragged_f32.restype = c_int
+    lib.opseq_stream_step_ragged_f32.argtypes = [fp, fp, fp, fp, fp, fp, c_void_p, c_size_t, c_int, c_int, c_int, c_int,
+                                                 c_int, c_int, c_void_p]
+    lib.opnet_online_encode_ragged_f32.restype = c_int
+    lib.opnet_online_encode_ragged_f32.argtypes = [fp, fp, fp, fp, fp, c_int, fp, fp, c_int, fp, c_int, c_int, c_int, c_int,
+                                                   c_float, fp, c_void_p]
     lib.opseq_stream_input_product_f32.restype = c_int
     lib.opseq_stream_input_product_f32.argtypes = [fp, fp, fp, c_void_p, c_size_t, c_int, c_int, c_int, c_int, c_int, c_int,
                                                    c_void_p]
@@ -322,12 +331,13 @@ EXPORTS = [
     "opnet_train_forward_f32", "opnet_train_backward_f32", "opnet_l1_loss_f32", "opnet_smooth_l1_loss_f32", "opnet_adam_step_f32", "opnet_adam_multi_step_f32",
     "opnet_adam_multi_step_guarded_f32", "opnet_dp_guard_f32", "opnet_xcd4_status_offset", "opnet_train_status_offset", "opnet_xcd4_enable", "opnet_xcd4_enabled",
     "opnet_mlp_pack_weights_f32", "opnet_mlp_forward_f32",
-    "opnet_stream_state_floats", "opnet_stream_workspace_bytes", "opnet_stream_step_f32",
-    "opnet_online_encode_f32",
+    "opnet_stream_state_floats", "opnet_stream_workspace_bytes", "opnet_stream_step_f32", "opnet_stream_step_ragged_f32",
+    "opnet_online_encode_f32", "opnet_online_encode_ragged_f32",
     "opnet_mlp_train_pack_weights_f32", "opnet_mlp_train_forward_f32", "opnet_mlp_train_backward_f32",
     "opseq_lstm_stack_packed_bytes", "opseq_lstm_stack_workspace_bytes", "opseq_lstm_stack_pack_weights_f32",
     "opseq_lstm_stack_forward_f32", "opseq_lstm_stack_forward_graph_f32", "opseq_graph_cache_clear",
-    "opseq_stream_state_floats", "opseq_stream_workspace_bytes", "opseq_stream_step_f32", "opseq_stream_input_product_f32",
+    "opseq_stream_state_floats", "opseq_stream_workspace_bytes", "opseq_stream_step_f32", "opseq_stream_step_ragged_f32",
+    "opseq_stream_input_product_f32",
     "opseq_xcd_supported", "opseq_xcd_enable", "opseq_xcd_max_batch", "opseq_xcd_packed_bytes", "opseq_xcd_workspace_bytes",
     "opseq_xcd_status_offset", "opseq_xcd_pack_weights_f32", "opseq_xcd_forward_f32", "opseq_lstm_stack_train_status_offset", "opseq_xcd_set_trace",
     "opseq_xcdt_supported", "opseq_xcdt_enable", "opseq_xcdt_max_batch", "opseq_xcdt_packed_bytes", "opseq_xcdt_workspace_bytes",

@@ -16,6 +16,9 @@
 // full, and encoding frame j with the row as it stands after all k frames gives the bits of encoding it with the row as
 // it stood after frame j: opnet_online_learn updates the rows first (one workgroup walks a stream's k frames), then
 // opnet_online_encode encodes every (stream, frame) independently (one wave each).  Both are deterministic.
+//
+// Ragged calls (opnet_online_encode_ragged_f32) give stream i len[i] of the k frames (clamped to [0, k]): a frame
+// j >= len[i] is padding and counts as n_det = 0, so it appends nothing to a learned row and encodes as zeros.
 #pragma once
 
 #define ONLINE_SLOTS 15
@@ -28,6 +31,7 @@ struct OnlineArgs {
     const float *scores;              // [n][k][md]
     const long long *labels;          // [n][k][md]
     const int32_t *n_det;             // [n][k]
+    const int32_t *len;               // [n] frames per stream (ragged calls), or null: k each
     const int32_t *slots;             // [n]
     int32_t *tables;                  // [capacity][16]
     const uint8_t *cone;              // [num_classes]
@@ -41,6 +45,9 @@ __device__ __forceinline__ int online_class(long long label)
 {
     return (label >= 0 && label < 0x7fffffffLL) ? (int)label : -1;
 }
+
+// the frames of stream i that hold detections: k, or len[i] clamped to [0, k]
+__device__ __forceinline__ int online_frames(const OnlineArgs &a, int i) { return a.len ? min(max(a.len[i], 0), a.k) : a.k; }
 
 // n workgroups x 256: workgroup i appends the new classes of stream i's k frames to its learned table row, in frame
 // order, each frame's ascending.  A round finds the smallest (frame, class) over the kept rows of the chunk whose class
@@ -68,8 +75,9 @@ __global__ void __launch_bounds__(256) opnet_online_learn(const OnlineArgs a)
     __syncthreads();
     int used = used_s;
     const int md = a.md;
-    for (int f0 = 0; f0 < a.k && used < ONLINE_SLOTS; f0 += ONLINE_LEARN_FRAMES) {
-        const int F = min(ONLINE_LEARN_FRAMES, a.k - f0);
+    const int kv = online_frames(a, i);                     // frames past it are padding: nothing to learn from
+    for (int f0 = 0; f0 < kv && used < ONLINE_SLOTS; f0 += ONLINE_LEARN_FRAMES) {
+        const int F = min(ONLINE_LEARN_FRAMES, kv - f0);
         const long frame0 = (long)i * a.k + f0;             // first (stream, frame) of the chunk
         if (tid < F) {
             nd[tid] = min(max(a.n_det[frame0 + tid], 0), md);
@@ -127,7 +135,8 @@ __global__ void __launch_bounds__(256) opnet_online_encode(const OnlineArgs a)
     for (int e = 0; e < ONLINE_SLOTS; ++e) tab[e] = row[e];
     const int md = a.md;
     const long base = item * md;
-    const int nd = min(max(a.n_det[item], 0), md);
+    // a padding frame of a ragged call has no detections
+    const int nd = (int)(item - (long)i * a.k) < online_frames(a, i) ? min(max(a.n_det[item], 0), md) : 0;
 
     // score cut: a count over the first n_det rows, then a prefix
     int kept = 0;

@@ -366,6 +366,33 @@ __device__ __forceinline__ float lstm_cell(float gi, float gf, float gg, float g
     return o * fast_tanh(c);
 }
 
+// Ragged stream steps (opnet_stream_step_ragged_f32): clip b's stream has len[b] frames of the call's T, and its column
+// freezes from frame len[b] on - the cell writes h_prev to the h slot the step writes and keeps c_old, so the final ring
+// holds the state after len[b] frames.  Columns past B never freeze.  t < len[b] is in range for any len[b] (a negative or
+// too large length acts as 0 or T): no access depends on it.
+__device__ __forceinline__ bool column_live(const int32_t *len, int B, long b, int t) { return b >= B || t < len[b]; }
+
+// lstm_cell_g for the ragged step kernels, with the contractions the compiler makes in the uniform kernels written out:
+// c = fma(f, c_old, i * g) and tanh's 1 - 2 r = fma(-2, r, 1).  Left to itself, the compiler pairs f * c_old and i * g
+// into one packed multiply once c feeds the ragged select, and the sum then rounds differently.
+#if OPNET_FAST_GATES
+__device__ __forceinline__ float tanh_fused(float x) { return __builtin_fmaf(-2.0f, __builtin_amdgcn_rcpf(1.0f + __expf(2.0f * x)), 1.0f); }
+#else
+__device__ __forceinline__ float tanh_fused(float x) { return tanhf(x); }
+#endif
+__device__ __forceinline__ float lstm_cell_fused(float gi, float gf, float gg, float go, float c_old, float *c_out,
+                                                 float4 *gates)
+{
+    const float i = fast_sigmoid(gi);
+    const float f = fast_sigmoid(gf);
+    const float g = tanh_fused(gg);
+    const float o = fast_sigmoid(go);
+    const float c = __builtin_fmaf(f, c_old, i * g);
+    *c_out = c;
+    *gates = make_float4(i, f, g, o);
+    return o * tanh_fused(c);
+}
+
 // history slots: inference keeps two parity slots per state buffer, training keeps every step
 __device__ __forceinline__ long slot_prev(const StepArgs &a, int t) { return a.train ? t : ((t + 1) & 1); }
 __device__ __forceinline__ long slot_out(const StepArgs &a, int t) { return a.train ? t + 1 : (t & 1); }
@@ -502,8 +529,8 @@ __device__ __forceinline__ void role_output_head(const StepArgs &a, const int s,
 // grid.x = n2 (LSTM2 tiles, longest K first) + n1 (LSTM1 tiles) + 2 heads ; grid.y <= row blocks
 // (a workgroup walks row blocks rb = blockIdx.y, blockIdx.y + gridDim.y, ... with its weights held
 // in registers).
-template <int CH, int NW>
-__device__ __forceinline__ void opnet_step_body(const StepArgs &a, const int s)
+template <int CH, int NW, bool RAGGED = false>
+__device__ __forceinline__ void opnet_step_body(const StepArgs &a, const int s, const int32_t *len = nullptr)
 {
     __shared__ __attribute__((aligned(16))) float lds[NW * 8 * 64 + 32 * 16];
     float *part = lds;
@@ -543,12 +570,17 @@ __device__ __forceinline__ void opnet_step_body(const StepArgs &a, const int s)
             const float4 *hprev = a.h2buf + (slot_prev(a, t) * a.RB + rb) * (H2 * 8);
             // epilogue operands are fetched before the MFMA phase so their latency hides under it
             float4 xa, xb;
-            float c_old = 0.f;
+            float c_old = 0.f, h_old = 0.f;
+            bool live = true;
             if (tid < 128) {
                 const float4 *x2 = a.x2buf + (slot_x2(a, t) * a.RB + rb) * 64 + clip;
                 xa = x2[0];
                 xb = x2[32];
                 c_old = a.c2[((cslot_prev(a, t) * a.RB + rb) * H2 + unit) * 32 + clip];
+                if constexpr (RAGGED) {
+                    live = column_live(len, a.B, rb * 32L + clip, t);
+                    h_old = ((const float *)hprev)[((long)tile * 32 + clip) * 4 + quarter];
+                }
             }
             if (a.mlp) {
                 // hidden = relu(hidden_layer(frames_boxes)) (learned_models.py:83): no recurrence, the
@@ -585,7 +617,14 @@ __device__ __forceinline__ void opnet_step_body(const StepArgs &a, const int s)
                 }
                 float c = c_old;
                 float4 gs;
-                const float h = lstm_cell_g(g[0], g[1], g[2], g[3], &c, &gs);
+                float h;
+                if constexpr (RAGGED) {   // selects, not 0/1 products: a padding frame's gates may be NaN
+                    h = lstm_cell_fused(g[0], g[1], g[2], g[3], c_old, &c, &gs);
+                    h = live ? h : h_old;
+                    c = live ? c : c_old;
+                } else {
+                    h = lstm_cell_g(g[0], g[1], g[2], g[3], &c, &gs);
+                }
                 a.c2[((cslot_out(a, t) * a.RB + rb) * H2 + unit) * 32 + clip] = c;
                 if (a.train) a.g2save[(((long)t * a.RB + rb) * H2 + unit) * 32 + clip] = gs;
                 float *hout = (float *)(a.h2buf + (slot_out(a, t) * a.RB + rb) * (H2 * 8));
@@ -607,16 +646,31 @@ __device__ __forceinline__ void opnet_step_body(const StepArgs &a, const int s)
         for (int rb = blockIdx.y; rb < a.RB; rb += gridDim.y) {
             const float4 *xsrc = a.xp + ((long)t * a.RB + rb) * (OPNET_KXQ * 32);
             const float4 *hprev = a.h1buf + (slot_prev(a, t) * a.RB + rb) * (H1 * 8);
-            float c_old = 0.f;
-            if (tid < 128) c_old = a.c1[((cslot_prev(a, t) * a.RB + rb) * H1 + unit) * 32 + clip];
+            float c_old = 0.f, h_old = 0.f;
+            bool live = true;
+            if (tid < 128) {
+                c_old = a.c1[((cslot_prev(a, t) * a.RB + rb) * H1 + unit) * 32 + clip];
+                if constexpr (RAGGED) {
+                    live = column_live(len, a.B, rb * 32L + clip, t);
+                    h_old = ((const float *)hprev)[((long)tile * 32 + clip) * 4 + quarter];
+                }
+            }
             gemm16_rb(a0, a_qb, A, xsrc, OPNET_KXQ / 4, hprev, ks, part, s, a.B - rb * 32 > 16);
             __syncthreads();
             TRACE_STAMP(4);
             if (tid < 128) {
                 float c = c_old;
                 float4 gs;
-                const float h = lstm_cell_g(part_sum<NW>(part, half * 4 + 0, el), part_sum<NW>(part, half * 4 + 1, el),
-                                            part_sum<NW>(part, half * 4 + 2, el), part_sum<NW>(part, half * 4 + 3, el), &c, &gs);
+                float h;
+                if constexpr (RAGGED) {
+                    h = lstm_cell_fused(part_sum<NW>(part, half * 4 + 0, el), part_sum<NW>(part, half * 4 + 1, el),
+                                        part_sum<NW>(part, half * 4 + 2, el), part_sum<NW>(part, half * 4 + 3, el), c_old, &c, &gs);
+                    h = live ? h : h_old;
+                    c = live ? c : c_old;
+                } else {
+                    h = lstm_cell_g(part_sum<NW>(part, half * 4 + 0, el), part_sum<NW>(part, half * 4 + 1, el),
+                                    part_sum<NW>(part, half * 4 + 2, el), part_sum<NW>(part, half * 4 + 3, el), &c, &gs);
+                }
                 a.c1[((cslot_out(a, t) * a.RB + rb) * H1 + unit) * 32 + clip] = c;
                 if (a.train) a.g1save[(((long)t * a.RB + rb) * H1 + unit) * 32 + clip] = gs;
                 float *hout = (float *)(a.h1buf + (slot_out(a, t) * a.RB + rb) * (H1 * 8));
@@ -636,6 +690,13 @@ template <int CH, int NW = OPNET_NW>
 __global__ void __launch_bounds__(NW * 64) opnet_step(const StepArgs a, const int s)
 {
     opnet_step_body<CH, NW>(a, s);
+}
+
+// the ragged form (stream steps with per-stream lengths len [B], device): the same body with the column freeze compiled in
+template <int CH, int NW = OPNET_NW>
+__global__ void __launch_bounds__(NW * 64) opnet_step_ragged(const StepArgs a, const int s, const int32_t *len)
+{
+    opnet_step_body<CH, NW, true>(a, s, len);
 }
 
 // The same step with SCALAR arguments only (two base pointers + the shape), so that the compiler's kernarg preloading
@@ -734,8 +795,8 @@ __device__ __forceinline__ float part_sum2(const float *__restrict__ part, int r
 }
 
 // grid.x = n2/2 (LSTM2 tile pairs) + n1/2 (LSTM1 tile pairs) + 2 heads ; requires H1 % 8 == 0, H2 % 8 == 0, !mlp
-template <int CH>
-__global__ void __launch_bounds__(OPNET_THREADS) opnet_step_wide(const StepArgs a, const int s)
+template <int CH, bool RAGGED>
+__device__ __forceinline__ void opnet_step_wide_body(const StepArgs &a, const int s, const int32_t *len)
 {
     __shared__ __attribute__((aligned(16))) float lds[OPNET_NW * 16 * 64 + 32 * 16];
     float *part = lds;
@@ -772,6 +833,12 @@ __global__ void __launch_bounds__(OPNET_THREADS) opnet_step_wide(const StepArgs 
             const float4 *x2 = a.x2buf + (slot_x2(a, t) * a.RB + rb) * 64 + clip;
             const float4 xa = x2[0], xb = x2[32];
             const float c_old = a.c2[((cslot_prev(a, t) * a.RB + rb) * H2 + unit) * 32 + clip];
+            float h_old = 0.f;
+            bool live = true;
+            if constexpr (RAGGED) {
+                live = column_live(len, a.B, rb * 32L + clip, t);
+                h_old = ((const float *)hprev)[((long)(2 * bx + tsel) * 32 + clip) * 4 + quarter];
+            }
             gemm32_rb(a0, a1, a_qb, A0, A1, hprev, nh, hprev, ks, part, a.B - rb * 32 > 16);
             __syncthreads();
             float g[4];
@@ -788,7 +855,14 @@ __global__ void __launch_bounds__(OPNET_THREADS) opnet_step_wide(const StepArgs 
             }
             float c = c_old;
             float4 gs;
-            const float h = lstm_cell_g(g[0], g[1], g[2], g[3], &c, &gs);
+            float h;
+            if constexpr (RAGGED) {
+                h = lstm_cell_fused(g[0], g[1], g[2], g[3], c_old, &c, &gs);
+                h = live ? h : h_old;
+                c = live ? c : c_old;
+            } else {
+                h = lstm_cell_g(g[0], g[1], g[2], g[3], &c, &gs);
+            }
             a.c2[((cslot_out(a, t) * a.RB + rb) * H2 + unit) * 32 + clip] = c;
             if (a.train) a.g2save[(((long)t * a.RB + rb) * H2 + unit) * 32 + clip] = gs;
             float *hout = (float *)(a.h2buf + (slot_out(a, t) * a.RB + rb) * (H2 * 8));
@@ -813,12 +887,26 @@ __global__ void __launch_bounds__(OPNET_THREADS) opnet_step_wide(const StepArgs 
             const float4 *xsrc = a.xp + ((long)t * a.RB + rb) * (OPNET_KXQ * 32);
             const float4 *hprev = a.h1buf + (slot_prev(a, t) * a.RB + rb) * (H1 * 8);
             const float c_old = a.c1[((cslot_prev(a, t) * a.RB + rb) * H1 + unit) * 32 + clip];
+            float h_old = 0.f;
+            bool live = true;
+            if constexpr (RAGGED) {
+                live = column_live(len, a.B, rb * 32L + clip, t);
+                h_old = ((const float *)hprev)[((long)(2 * pr + tsel) * 32 + clip) * 4 + quarter];
+            }
             gemm32_rb(a0, a1, a_qb, A0, A1, xsrc, OPNET_KXQ / 4, hprev, ks, part, a.B - rb * 32 > 16);
             __syncthreads();
             float c = c_old;
             float4 gs;
-            const float h = lstm_cell_g(part_sum2(part, ereg + 0, el), part_sum2(part, ereg + 1, el),
-                                        part_sum2(part, ereg + 2, el), part_sum2(part, ereg + 3, el), &c, &gs);
+            float h;
+            if constexpr (RAGGED) {
+                h = lstm_cell_fused(part_sum2(part, ereg + 0, el), part_sum2(part, ereg + 1, el),
+                                    part_sum2(part, ereg + 2, el), part_sum2(part, ereg + 3, el), c_old, &c, &gs);
+                h = live ? h : h_old;
+                c = live ? c : c_old;
+            } else {
+                h = lstm_cell_g(part_sum2(part, ereg + 0, el), part_sum2(part, ereg + 1, el),
+                                part_sum2(part, ereg + 2, el), part_sum2(part, ereg + 3, el), &c, &gs);
+            }
             a.c1[((cslot_out(a, t) * a.RB + rb) * H1 + unit) * 32 + clip] = c;
             if (a.train) a.g1save[(((long)t * a.RB + rb) * H1 + unit) * 32 + clip] = gs;
             float *hout = (float *)(a.h1buf + (slot_out(a, t) * a.RB + rb) * (H1 * 8));
@@ -830,6 +918,19 @@ __global__ void __launch_bounds__(OPNET_THREADS) opnet_step_wide(const StepArgs 
     } else if (bx == p2 + p1 + 1) {
         role_output_head<CH>(a, s, part);
     }   // beyond: padding workgroups
+}
+
+template <int CH>
+__global__ void __launch_bounds__(OPNET_THREADS) opnet_step_wide(const StepArgs a, const int s)
+{
+    opnet_step_wide_body<CH, false>(a, s, nullptr);
+}
+
+// the ragged form of the wide step (see opnet_step_ragged)
+template <int CH>
+__global__ void __launch_bounds__(OPNET_THREADS) opnet_step_wide_ragged(const StepArgs a, const int s, const int32_t *len)
+{
+    opnet_step_wide_body<CH, true>(a, s, len);
 }
 
 // ------------------------------------------------------------------------------------------------

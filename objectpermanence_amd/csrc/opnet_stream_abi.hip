@@ -18,10 +18,22 @@ extern "C" size_t opnet_stream_workspace_bytes(int n, int k, int H1, int H2)
     return workspace_layout(n, k, H1, H2).total;
 }
 
-// prologue -> k + 3 step launches -> write-back: k + 5 dependent launches on `stream`, no host synchronisation
-extern "C" int opnet_stream_step_f32(const float *boxes, const int32_t *slots, float *state, const float *packed, float *y,
-                                     float *logits, void *workspace, size_t workspace_bytes, int n, int k, int capacity, int H1,
-                                     int H2, int mlp, void *stream)
+// the ragged form (opnet_step_ragged / opnet_step_wide_ragged) of the step kernel step_kernel picks for this shape
+typedef void (*opnet_step_ragged_fn)(const StepArgs, const int, const int32_t *);
+static opnet_step_ragged_fn step_kernel_ragged(const StepArgs &a)
+{
+    const char *force = getenv("OPNET_STEP_CH");
+    const bool small_chunks = force ? atoi(force) == 4 : a.RB >= 2;
+    if (step_is_wide(a)) return small_chunks ? opnet_step_wide_ragged<4> : opnet_step_wide_ragged<8>;
+    if (step_is_nw8(a)) return opnet_step_ragged<4, 8>;
+    return small_chunks ? opnet_step_ragged<4> : opnet_step_ragged<8>;
+}
+
+// prologue -> k + 3 step launches -> write-back: k + 5 dependent launches on `stream`, no host synchronisation.  lengths
+// (device [n], or null for the uniform call) selects the ragged step and write-back kernels.
+static int opnet_stream_step(const float *boxes, const int32_t *slots, const int32_t *lengths, float *state,
+                             const float *packed, float *y, float *logits, void *workspace, size_t workspace_bytes, int n,
+                             int k, int capacity, int H1, int H2, int mlp, void *stream)
 {
     if (int rc = check_dims(n, k, H1, H2)) return rc;
     if (capacity <= 0) return fail(OPNET_ESHAPE, "capacity=%d must be positive", capacity);
@@ -29,8 +41,9 @@ extern "C" int opnet_stream_step_f32(const float *boxes, const int32_t *slots, f
     if (mlp != 0 && mlp != 1) return fail(OPNET_EINVAL, "mlp must be 0 or 1 (got %d)", mlp);
     if (!boxes || !slots || !state || !packed || !y || !logits || !workspace) return fail(OPNET_EINVAL, "null pointer");
     if (!aligned16(state) || !aligned16(packed) || !aligned16(y) || !aligned16(workspace) || (((uintptr_t)boxes) & 7u) ||
-        (((uintptr_t)slots) & 3u) || (((uintptr_t)logits) & 3u))
-        return fail(OPNET_EINVAL, "state/packed/y/workspace must be 16-byte, boxes 8-byte and slots/logits 4-byte aligned");
+        (((uintptr_t)slots) & 3u) || (((uintptr_t)logits) & 3u) || (((uintptr_t)lengths) & 3u))
+        return fail(OPNET_EINVAL, "state/packed/y/workspace must be 16-byte, boxes 8-byte and slots/lengths/logits 4-byte "
+                                  "aligned");
     const WorkspaceLayout W = workspace_layout(n, k, H1, H2);
     if (workspace_bytes < W.total) return fail(OPNET_EWORKSPACE, "workspace %zu B < %zu B", workspace_bytes, W.total);
 
@@ -54,13 +67,38 @@ extern "C" int opnet_stream_step_f32(const float *boxes, const int32_t *slots, f
     opnet_stream_prologue<<<dim3(k + G, a.RB), 256, 0, st>>>(s);
     // the chain's step kernel for this shape; the kernarg-preload form (opnet_step_pl) is left out: it carves its buffers
     // from the chain's own workspace, and computes the same body as opnet_step<4, 8>
-    const opnet_step_fn stepk = step_kernel(a);
     const dim3 grid = step_grid(a);
-    for (int t = 0; t < k + 3; ++t) stepk<<<grid, step_threads(a), 0, st>>>(a, t);
+    if (lengths) {
+        const opnet_step_ragged_fn stepk = step_kernel_ragged(a);
+        for (int t = 0; t < k + 3; ++t) stepk<<<grid, step_threads(a), 0, st>>>(a, t, lengths);
+    } else {
+        const opnet_step_fn stepk = step_kernel(a);
+        for (int t = 0; t < k + 3; ++t) stepk<<<grid, step_threads(a), 0, st>>>(a, t);
+    }
     const long items = (long)a.B * OPNET_SLOTS * k > (long)a.RB * 32 * (H1 + H2) / 4 ? (long)a.B * OPNET_SLOTS * k
                                                                                      : (long)a.RB * 32 * (H1 + H2) / 4;
     const unsigned wb = (unsigned)((items + 255) / 256 > 1024 ? 1024 : (items + 255) / 256);
-    opnet_stream_writeback<<<wb, 256, 0, st>>>(s);
+    if (lengths) opnet_stream_writeback_ragged<<<wb, 256, 0, st>>>(s, lengths);
+    else opnet_stream_writeback<<<wb, 256, 0, st>>>(s);
     HIP_TRY(hipGetLastError());
     return OPNET_OK;
+}
+
+extern "C" int opnet_stream_step_f32(const float *boxes, const int32_t *slots, float *state, const float *packed, float *y,
+                                     float *logits, void *workspace, size_t workspace_bytes, int n, int k, int capacity, int H1,
+                                     int H2, int mlp, void *stream)
+{
+    return opnet_stream_step(boxes, slots, nullptr, state, packed, y, logits, workspace, workspace_bytes, n, k, capacity, H1,
+                             H2, mlp, stream);
+}
+
+// stream i advances by lengths[i] of the k frames (device int32 [n], clamped to [0, k] by the kernels)
+extern "C" int opnet_stream_step_ragged_f32(const float *boxes, const int32_t *slots, const int32_t *lengths, float *state,
+                                            const float *packed, float *y, float *logits, void *workspace,
+                                            size_t workspace_bytes, int n, int k, int capacity, int H1, int H2, int mlp,
+                                            void *stream)
+{
+    if (!lengths) return fail(OPNET_EINVAL, "null pointer: lengths");
+    return opnet_stream_step(boxes, slots, lengths, state, packed, y, logits, workspace, workspace_bytes, n, k, capacity, H1,
+                             H2, mlp, stream);
 }

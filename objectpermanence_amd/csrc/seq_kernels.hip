@@ -46,8 +46,10 @@ struct StackArgs {
 // one launch after layer l-1 produced h_t, one before the recurrent role consumes it - and the head t = s - (2L - 1).
 // CH = register chunk (see load_a_chunk), NW = waves per workgroup: <4, 8> for one row block (a latency chain: 8 waves
 // halve the MFMA chain and need one fetch round trip), <4, 4> above.
-template <int CH, int NW = OPNET_NW>
-__global__ void __launch_bounds__(NW * 64) lstm_stack_step(const StackArgs a, const int s)
+// RAGGED: the stream steps' per-stream lengths len [B] (opseq_stream_step_ragged_f32): layer l's cell at t = s - 2l freezes
+// clip b's column from t = len[b] on, as opnet_step_ragged does (opnet_kernels.hip column_live).
+template <int CH, int NW, bool RAGGED>
+__device__ __forceinline__ void lstm_stack_step_body(const StackArgs &a, const int s, const int32_t *len)
 {
     __shared__ __attribute__((aligned(16))) float part[NW * 8 * 64];
     const int tid = threadIdx.x;
@@ -111,19 +113,32 @@ __global__ void __launch_bounds__(NW * 64) lstm_stack_step(const StackArgs a, co
             const long co = a.train ? t + 1 : 0, cp = a.train ? t : 0;
             const float4 *xseg = a.xp + ((long)t * a.RB + rb) * ((long)nhx * 128);      // layer 0 only (nhx = 0 above it)
             const float4 *hprev = ly.hbuf + (sp * a.RB + rb) * ((long)H * 8);
-            float c_old = 0.f;
+            float c_old = 0.f, h_old = 0.f;
+            bool live = true;
             float4 xg = make_float4(0.f, 0.f, 0.f, 0.f);
             if (tid < 128) {
                 c_old = ly.c[((cp * a.RB + rb) * H + unit) * 32 + clip];
                 if (ly.xg) xg = ly.xg[(((long)t * a.RB + rb) * H + unit) * 32 + clip];
+                if constexpr (RAGGED) {
+                    live = column_live(len, a.B, rb * 32L + clip, t);
+                    h_old = ((const float *)hprev)[((long)tile * 32 + clip) * 4 + quarter];
+                }
             }
             gemm16_rb(a0, a_qb, A, xseg, nhx, hprev, ks, part, s, a.B - rb * 32 > 16);
             __syncthreads();
             if (tid < 128) {
                 float c = c_old;
                 float4 gs;
-                const float h = lstm_cell_g(part_sum<NW>(part, half * 4 + 0, el) + xg.x, part_sum<NW>(part, half * 4 + 1, el) + xg.y,
-                                            part_sum<NW>(part, half * 4 + 2, el) + xg.z, part_sum<NW>(part, half * 4 + 3, el) + xg.w, &c, &gs);
+                float h;
+                if constexpr (RAGGED) {   // selects, not 0/1 products: a padding frame's gates may be NaN
+                    h = lstm_cell_fused(part_sum<NW>(part, half * 4 + 0, el) + xg.x, part_sum<NW>(part, half * 4 + 1, el) + xg.y,
+                                        part_sum<NW>(part, half * 4 + 2, el) + xg.z, part_sum<NW>(part, half * 4 + 3, el) + xg.w, c_old, &c, &gs);
+                    h = live ? h : h_old;
+                    c = live ? c : c_old;
+                } else {
+                    h = lstm_cell_g(part_sum<NW>(part, half * 4 + 0, el) + xg.x, part_sum<NW>(part, half * 4 + 1, el) + xg.y,
+                                    part_sum<NW>(part, half * 4 + 2, el) + xg.z, part_sum<NW>(part, half * 4 + 3, el) + xg.w, &c, &gs);
+                }
                 ly.c[((co * a.RB + rb) * H + unit) * 32 + clip] = c;
                 if (a.train) ly.gsave[(((long)t * a.RB + rb) * H + unit) * 32 + clip] = gs;
                 float *hout = (float *)(ly.hbuf + (so * a.RB + rb) * ((long)H * 8));
@@ -157,6 +172,18 @@ __global__ void __launch_bounds__(NW * 64) lstm_stack_step(const StackArgs a, co
             if (rb + (int)gridDim.y < a.RB) __syncthreads();
         }
     }
+}
+
+template <int CH, int NW = OPNET_NW>
+__global__ void __launch_bounds__(NW * 64) lstm_stack_step(const StackArgs a, const int s)
+{
+    lstm_stack_step_body<CH, NW, false>(a, s, nullptr);
+}
+
+template <int CH, int NW = OPNET_NW>
+__global__ void __launch_bounds__(NW * 64) lstm_stack_step_ragged(const StackArgs a, const int s, const int32_t *len)
+{
+    lstm_stack_step_body<CH, NW, true>(a, s, len);
 }
 
 // x [B][T][K] row-major -> xp [t][rb][KP/4][clip][4], K padded with zeros to KP (multiple of 16),

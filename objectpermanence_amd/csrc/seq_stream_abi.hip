@@ -31,6 +31,15 @@ static void seq_stream_input_product(const float *x, const float *packed, float4
     stack_hoisted_input_tiled(x, packed, w, xg, n, k, L, KX, H, st);
 }
 
+// the ragged form (lstm_stack_step_ragged) of the step kernel stack_step_kernel picks for this many row blocks
+typedef void (*stack_step_ragged_fn)(const StackArgs, const int, const int32_t *);
+static stack_step_ragged_fn stack_step_kernel_ragged(int RB)
+{
+    const char *force = getenv("OPNET_STEP_CH");
+    if (stack_is_nw8(RB)) return lstm_stack_step_ragged<4, 8>;
+    return (force ? atoi(force) == 4 : RB >= 2) ? lstm_stack_step_ragged<4> : lstm_stack_step_ragged<8>;
+}
+
 static bool seq_stream_takes_skinny(int n, int k)
 {
     return seq_stream_skinny_rows(n, k) <= env_int("OPSEQ_STREAM_SKINNY_MAX_ROWS", SEQ_STREAM_SKINNY_MAX_ROWS);
@@ -58,18 +67,18 @@ extern "C" size_t opseq_stream_workspace_bytes(int n, int k, int L, int KX, int 
 }
 
 // [hoisted input product] -> prologue -> k + 2L - 1 step launches -> write-back, dependent launches on `stream`, no host
-// synchronisation
-extern "C" int opseq_stream_step_f32(const float *x, const int32_t *slots, float *state, const float *packed, float *y,
-                                     void *workspace, size_t workspace_bytes, int n, int k, int capacity, int L, int KX,
-                                     int H, void *stream)
+// synchronisation.  lengths (device [n], or null for the uniform call) selects the ragged step and write-back kernels.
+static int opseq_stream_step(const float *x, const int32_t *slots, const int32_t *lengths, float *state, const float *packed,
+                             float *y, void *workspace, size_t workspace_bytes, int n, int k, int capacity, int L, int KX,
+                             int H, void *stream)
 {
     if (int rc = check_seq_stream(n, k, L, KX, H)) return rc;
     if (capacity <= 0) return fail(OPNET_ESHAPE, "capacity=%d must be positive", capacity);
     if (!x || !slots || !state || !packed || !y || !workspace) return fail(OPNET_EINVAL, "null pointer");
     const bool hoist = stack_hoists_input(KX, H);
     if (!aligned16(state) || !aligned16(packed) || !aligned16(y) || !aligned16(workspace) || (((uintptr_t)slots) & 3u) ||
-        (((uintptr_t)x) & (hoist ? 15u : 3u)))
-        return fail(OPNET_EINVAL, "state/packed/y/workspace must be 16-byte aligned, slots 4-byte and x %d-byte",
+        (((uintptr_t)lengths) & 3u) || (((uintptr_t)x) & (hoist ? 15u : 3u)))
+        return fail(OPNET_EINVAL, "state/packed/y/workspace must be 16-byte aligned, slots/lengths 4-byte and x %d-byte",
                     hoist ? 16 : 4);
     const StackWorkspaceLayout W = stack_workspace_layout(n, k, L, KX, H);
     if (workspace_bytes < W.total) return fail(OPNET_EWORKSPACE, "workspace %zu B < %zu B", workspace_bytes, W.total);
@@ -95,13 +104,37 @@ extern "C" int opseq_stream_step_f32(const float *x, const int32_t *slots, float
     const int gather_items = L * (H / 4) * 32;
     const int G = (gather_items + 255) / 256 < 64 ? (gather_items + 255) / 256 : 64;
     seq_stream_prologue<<<dim3((hoist ? 0 : k) + G, a.RB), 256, 0, st>>>(s);
-    const stack_step_fn stepk = stack_step_kernel(a.RB);
-    for (int t = 0; t < k + 2 * L - 1; ++t) stepk<<<grid, stack_step_threads(a.RB), 0, st>>>(a, t);
+    if (lengths) {
+        const stack_step_ragged_fn stepk = stack_step_kernel_ragged(a.RB);
+        for (int t = 0; t < k + 2 * L - 1; ++t) stepk<<<grid, stack_step_threads(a.RB), 0, st>>>(a, t, lengths);
+    } else {
+        const stack_step_fn stepk = stack_step_kernel(a.RB);
+        for (int t = 0; t < k + 2 * L - 1; ++t) stepk<<<grid, stack_step_threads(a.RB), 0, st>>>(a, t);
+    }
     const long items = (long)n * k > (long)a.RB * 32 * L * (H / 4) ? (long)n * k : (long)a.RB * 32 * L * (H / 4);
     const unsigned wb = (unsigned)((items + 255) / 256 > 1024 ? 1024 : (items + 255) / 256);
-    seq_stream_writeback<<<wb, 256, 0, st>>>(s);
+    if (lengths) seq_stream_writeback_ragged<<<wb, 256, 0, st>>>(s, lengths);
+    else seq_stream_writeback<<<wb, 256, 0, st>>>(s);
     HIP_TRY(hipGetLastError());
     return OPNET_OK;
+}
+
+extern "C" int opseq_stream_step_f32(const float *x, const int32_t *slots, float *state, const float *packed, float *y,
+                                     void *workspace, size_t workspace_bytes, int n, int k, int capacity, int L, int KX,
+                                     int H, void *stream)
+{
+    return opseq_stream_step(x, slots, nullptr, state, packed, y, workspace, workspace_bytes, n, k, capacity, L, KX, H,
+                             stream);
+}
+
+// stream i advances by lengths[i] of the k frames (device int32 [n], clamped to [0, k] by the kernels)
+extern "C" int opseq_stream_step_ragged_f32(const float *x, const int32_t *slots, const int32_t *lengths, float *state,
+                                            const float *packed, float *y, void *workspace, size_t workspace_bytes, int n,
+                                            int k, int capacity, int L, int KX, int H, void *stream)
+{
+    if (!lengths) return fail(OPNET_EINVAL, "null pointer: lengths");
+    return opseq_stream_step(x, slots, lengths, state, packed, y, workspace, workspace_bytes, n, k, capacity, L, KX, H,
+                             stream);
 }
 
 // the hoisted layer-0 input product of a stream call alone, into the caller's xg: route 0 = as opseq_stream_step_f32 routes

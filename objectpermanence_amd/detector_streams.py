@@ -21,6 +21,10 @@ A stream's table row holds 15 class ids (-1 = free) and a mode:
             every other class of the clip appears in the first frame that has detections.  Otherwise the order is
             first-seen (frame by frame, ascending within a frame), not the clip's ascending order.
 
+Streams may advance by different numbers of frames in one call: `lengths` ([n], 0..k) on encode / step_detections, or a
+list of per-stream frame arrays [k_i, H, W, 3] for step.  Frames past a stream's length are padding: they count as frames
+without detections for the encoder (nothing is learned from them, they encode as zeros) and never reach the pool's state.
+
 `encode_detections_numpy` is the readable statement the kernel is held to bit for bit, as encode_boxes is to the native
 clip encoder.  step_detections and encode do not synchronise the host: slot ids go up through fresh pinned buffers, and
 nothing comes back down.
@@ -36,7 +40,7 @@ from . import _lib
 from .datasets import FRAME_SHAPES, MAX_OBJECTS, _cone_table
 from .learned_models import BaselineLstm, NonLinearLstm, OPNet, OPNetLstmMlp, _stream_ptr
 from .object_indices import SNITCH_INDEX
-from .streaming import LstmStackStreams, OPNetStreams
+from .streaming import LstmStackStreams, OPNetStreams, check_lengths, upload_async
 
 TABLE_INTS = 16                # OPNET_ONLINE_TABLE_INTS: 15 class ids + the mode
 MODE_FIXED, MODE_LEARNED = 0, 1
@@ -71,11 +75,23 @@ def _valid_class(c: int) -> bool:
     return 0 <= c < _CLASS_MAX
 
 
+def _valid_n_det(n_det: np.ndarray, lengths) -> np.ndarray:
+    """n_det with the padding frames of a ragged call (j >= lengths[i], clamped to [0, k]) counted as empty"""
+    if lengths is None:
+        return n_det
+    n_det = np.array(n_det, copy=True)
+    k = n_det.shape[1]
+    for i, L in enumerate(np.asarray(lengths).reshape(-1)):
+        n_det[i, min(max(int(L), 0), k):] = 0
+    return n_det
+
+
 def learn_tables_numpy(tables: np.ndarray, slots: Sequence[int], scores: np.ndarray, labels: np.ndarray, n_det: np.ndarray,
-                       score_thresh: float = SCORE_THRESHOLD) -> None:
+                       score_thresh: float = SCORE_THRESHOLD, lengths=None) -> None:
     """the learned-table update of one call, in place: tables [capacity, 16] int32, scores [n, k, md], labels [n, k, md],
     n_det [n, k].  Frame by frame, each learned row appends its frame's classes not yet in it, ascending, while entries
-    remain; fixed rows are left as they are."""
+    remain; fixed rows are left as they are.  lengths [n] (ragged calls): frames j >= lengths[i] have no detections."""
+    n_det = _valid_n_det(n_det, lengths)
     for i, slot in enumerate(slots):
         row = tables[slot]
         if row[15] != MODE_LEARNED:
@@ -123,12 +139,14 @@ def encode_frame_numpy(boxes: np.ndarray, labels: np.ndarray, kept: int, row: np
 
 def encode_detections_numpy(boxes: np.ndarray, scores: np.ndarray, labels: np.ndarray, n_det: np.ndarray,
                             slots: Sequence[int], tables: np.ndarray, cone_mask: np.ndarray, n_tracks: int,
-                            score_thresh: float = SCORE_THRESHOLD) -> np.ndarray:
+                            score_thresh: float = SCORE_THRESHOLD, lengths=None) -> np.ndarray:
     """The statement of opnet_online_encode_f32: padded detections of n streams x k frames (boxes [n, k, md, 4] fp32,
     scores [n, k, md] fp32, labels [n, k, md] int64, n_det [n, k]) and the streams' table rows tables[slots[i]] -> fp32
-    [n, k, 15, n_tracks].  Learned rows of `tables` are updated in place first (learn_tables_numpy)."""
+    [n, k, 15, n_tracks].  Learned rows of `tables` are updated in place first (learn_tables_numpy).  lengths [n]
+    (opnet_online_encode_ragged_f32): frames j >= lengths[i] count as n_det = 0, so they learn nothing and encode as zeros."""
     if n_tracks not in (5, 6):
         raise ValueError(f"n_tracks must be 5 or 6, got {n_tracks}")
+    n_det = _valid_n_det(n_det, lengths)
     learn_tables_numpy(tables, slots, scores, labels, n_det, score_thresh)
     n, k = scores.shape[:2]
     out = np.zeros((n, k, MAX_OBJECTS, n_tracks), dtype=np.float32)
@@ -145,6 +163,8 @@ class StreamResult(NamedTuple):
     logits: Optional[torch.Tensor]          # fp32 [n, 15, k] (OPNet and OPNetLstmMlp), else None
     x: torch.Tensor                         # the encoded model input [n, k, 15, n_tracks]
     detections: Optional[Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]]   # (boxes, scores, labels, n_det)
+    lengths: Optional[torch.Tensor] = None  # int32 [n] frames per stream of a ragged call (boxes_px, y, logits, x are 0
+                                            #   past them); None: every stream advanced by k
 
 
 class DetectorStreams:
@@ -208,9 +228,23 @@ class DetectorStreams:
 
     # -- encoding -----------------------------------------------------------------------------
     def _upload(self, a: np.ndarray) -> torch.Tensor:
-        """a host array on the device without a host sync: a fresh pinned copy, then an asynchronous copy on the current
-        stream (the caching host allocator keeps the pinned block until that copy has run)"""
-        return torch.from_numpy(np.ascontiguousarray(a)).pin_memory().to(self.device, non_blocking=True)
+        """a host array on the device without a host sync (streaming.upload_async)"""
+        return upload_async(a, self.device)
+
+    def _ids_and_lengths(self, idx: np.ndarray, lengths, k: int):
+        """(slots, lengths) on the device without a host sync: host lengths are checked and go up with the slot ids in one
+        pinned copy; an int32 device tensor [n] is taken as is"""
+        n = idx.size
+        if lengths is None:
+            return self._upload(idx.astype(np.int32)), None
+        if isinstance(lengths, torch.Tensor) and lengths.is_cuda:
+            if lengths.device != self.device:
+                raise ValueError(f"lengths are on {lengths.device}, the streams on {self.device}")
+            if lengths.dtype != torch.int32 or tuple(lengths.shape) != (n,):
+                raise ValueError(f"device lengths must be int32 [n={n}], got {lengths.dtype} {tuple(lengths.shape)}")
+            return self._upload(idx.astype(np.int32)), lengths.contiguous()
+        both = self._upload(np.concatenate([idx.astype(np.int32), check_lengths(lengths, n, k)]))
+        return both[:n], both[n:]
 
     def _check_detections(self, ids, boxes, scores, labels, n_det):
         for t, name, dt in ((boxes, "boxes", torch.float32), (scores, "scores", torch.float32),
@@ -232,57 +266,75 @@ class DetectorStreams:
             raise ValueError(f"n_det must be [{n}, {k}], got {tuple(n_det.shape)}")
         return idx, k, md
 
-    def _encode_into(self, out: torch.Tensor, slots: torch.Tensor, boxes, scores, labels, n_det) -> None:
+    def _encode_into(self, out: torch.Tensor, slots: torch.Tensor, boxes, scores, labels, n_det,
+                     lengths: Optional[torch.Tensor] = None) -> None:
         n, k, md = int(boxes.shape[0]), int(boxes.shape[1]), int(boxes.shape[2])
         boxes, scores, labels, n_det = (t.contiguous() for t in (boxes, scores, labels, n_det))
         assert out.is_contiguous() and tuple(out.shape) == (n, k, MAX_OBJECTS, self.n_tracks)
-        rc = _lib.load().opnet_online_encode_f32(
-            boxes.data_ptr(), scores.data_ptr(), labels.data_ptr(), n_det.data_ptr(), md, slots.data_ptr(),
-            self.tables.data_ptr(), self.capacity, self.cone_mask.data_ptr(), int(self.cone_mask.numel()), n, k,
-            self.n_tracks, self.score_thresh, out.data_ptr(), _stream_ptr(self.device))
-        _lib.check(rc, "opnet_online_encode_f32")
+        lib = _lib.load()
+        if lengths is None:
+            rc = lib.opnet_online_encode_f32(
+                boxes.data_ptr(), scores.data_ptr(), labels.data_ptr(), n_det.data_ptr(), md, slots.data_ptr(),
+                self.tables.data_ptr(), self.capacity, self.cone_mask.data_ptr(), int(self.cone_mask.numel()), n, k,
+                self.n_tracks, self.score_thresh, out.data_ptr(), _stream_ptr(self.device))
+            _lib.check(rc, "opnet_online_encode_f32")
+        else:
+            rc = lib.opnet_online_encode_ragged_f32(
+                boxes.data_ptr(), scores.data_ptr(), labels.data_ptr(), n_det.data_ptr(), lengths.data_ptr(), md,
+                slots.data_ptr(), self.tables.data_ptr(), self.capacity, self.cone_mask.data_ptr(),
+                int(self.cone_mask.numel()), n, k, self.n_tracks, self.score_thresh, out.data_ptr(), _stream_ptr(self.device))
+            _lib.check(rc, "opnet_online_encode_ragged_f32")
 
-    def _encode(self, ids, boxes, scores, labels, n_det):
+    def _encode(self, ids, boxes, scores, labels, n_det, lengths=None):
         idx, k, md = self._check_detections(ids, boxes, scores, labels, n_det)
         with torch.no_grad(), torch.cuda.device(self.device):
-            slots = self._upload(idx.astype(np.int32))
+            slots, lens = self._ids_and_lengths(idx, lengths, k)
             x = torch.empty((idx.size, k, MAX_OBJECTS, self.n_tracks), dtype=torch.float32, device=self.device)
-            self._encode_into(x, slots, boxes, scores, labels, n_det)
-        return slots, x
+            self._encode_into(x, slots, boxes, scores, labels, n_det, lens)
+        return slots, lens, x
 
     def encode(self, ids: Sequence[int], boxes: torch.Tensor, scores: torch.Tensor, labels: torch.Tensor,
-               n_det: torch.Tensor) -> torch.Tensor:
+               n_det: torch.Tensor, lengths=None) -> torch.Tensor:
         """the model input of k frames of detections (boxes [n, k, md, 4] fp32 pixels, scores [n, k, md] fp32, labels
         [n, k, md] int64, n_det [n, k] int32, padded as RoIHeads writes them) -> [n, k, 15, n_tracks].  Learned slot orders
-        are updated; the streams' states are not advanced.  No host sync."""
-        return self._encode(ids, boxes, scores, labels, n_det)[1]
+        are updated; the streams' states are not advanced.  lengths ([n] in 0..k, host or int32 device): frames past a
+        stream's length are padding, learn nothing and encode as zeros.  No host sync."""
+        return self._encode(ids, boxes, scores, labels, n_det, lengths)[2]
 
     # -- frames -------------------------------------------------------------------------------
-    def _advance(self, slots: torch.Tensor, x: torch.Tensor, detections) -> StreamResult:
+    def _advance(self, slots: torch.Tensor, x: torch.Tensor, detections,
+                 lengths: Optional[torch.Tensor] = None) -> StreamResult:
         n, k = int(x.shape[0]), int(x.shape[1])
         with torch.no_grad(), torch.cuda.device(self.device):
-            out = self.pool._step_slots(slots, x)
+            out = self.pool._step_slots(slots, x, lengths)
             y, logits = out if isinstance(out, tuple) else (out, None)
             px = torch.empty((n, k, 4), dtype=torch.int32, device=self.device)
             rc = _lib.load().opnet_postprocess_iou(y.data_ptr(), None, px.data_ptr(), None, None, n, k,
                                                    _stream_ptr(self.device))
             _lib.check(rc, "opnet_postprocess_iou")
-        return StreamResult(px, y, logits, x, detections)
+        return StreamResult(px, y, logits, x, detections, lengths)
 
     def step_detections(self, ids: Sequence[int], boxes: torch.Tensor, scores: torch.Tensor, labels: torch.Tensor,
-                        n_det: torch.Tensor) -> StreamResult:
-        """encode k frames of detections of your own detector (as `encode`) and advance the streams by them.  No host
-        sync."""
-        slots, x = self._encode(ids, boxes, scores, labels, n_det)
-        return self._advance(slots, x, (boxes, scores, labels, n_det))
+                        n_det: torch.Tensor, lengths=None) -> StreamResult:
+        """encode k frames of detections of your own detector (as `encode`) and advance the streams by them (stream i by
+        its first lengths[i] when lengths are given).  No host sync."""
+        slots, lens, x = self._encode(ids, boxes, scores, labels, n_det, lengths)
+        return self._advance(slots, x, (boxes, scores, labels, n_det), lens)
 
     def step(self, ids: Sequence[int], frames) -> StreamResult:
         """k frames per stream through the detector, the encoder and the pool: frames uint8 BGR [n, k, H, W, 3] (row i
         belongs to ids[i]; one shape for all).  The detector runs in passes of at most MAX_FRAMES_PER_PASS frames in
         stream-major order (whole streams per pass when k allows it), the encoder once per pass into its slice of x.
-        r.detections holds the padded detections used, [n, k, md, ...]."""
+        r.detections holds the padded detections used, [n, k, md, ...].
+
+        frames may also be a list of n per-stream arrays uint8 [k_i, H, W, 3] (k_i >= 0, one H, W): the detector then runs
+        on the sum(k_i) real frames only, in passes of at most MAX_FRAMES_PER_PASS, their detections are scattered into
+        [n, K = max k_i, md, ...] with n_det = 0 on padding, and the encoder and the pool run once with the lengths k_i
+        (r.lengths)."""
         if self.detector is None:
             raise RuntimeError("DetectorStreams.step needs a detector: DetectorStreams(model, detector=...)")
+        if isinstance(frames, (list, tuple)):
+            return self._step_ragged(ids, frames)
         frames = np.asarray(frames)
         if frames.dtype != np.uint8 or frames.ndim != 5 or frames.shape[4] != 3 or frames.shape[1] < 1:
             raise ValueError(f"frames must be uint8 [n, k>=1, H, W, 3], got {frames.dtype} {tuple(frames.shape)}")
@@ -310,3 +362,42 @@ class DetectorStreams:
                 parts.append((b, s, l, nd))
             det = tuple(torch.cat([p[q] for p in parts]).view(n, k, *parts[0][q].shape[1:]) for q in range(4))
         return self._advance(slots, x, det)
+
+    def _step_ragged(self, ids: Sequence[int], frames) -> StreamResult:
+        idx = self.pool.slots.check(ids)
+        n = idx.size
+        if len(frames) != n:
+            raise ValueError(f"frames hold {len(frames)} streams, ids {n}")
+        arrays = [np.asarray(f) for f in frames]
+        for f in arrays:
+            if f.dtype != np.uint8 or f.ndim != 4 or f.shape[3] != 3:
+                raise ValueError(f"each stream's frames must be uint8 [k_i, H, W, 3], got {f.dtype} {tuple(f.shape)}")
+        if len({f.shape[1:] for f in arrays if f.shape[0] > 0}) > 1:
+            raise ValueError("the frames of one call must share one H, W")
+        ks = np.array([f.shape[0] for f in arrays], dtype=np.int32)
+        K = int(ks.max())
+        if K < 1:
+            raise ValueError("a ragged step needs at least one frame")
+        # the real frames, stream-major, and the padded row (i * K + j) each one lands in
+        flat = [f[j] for f in arrays for j in range(f.shape[0])]
+        dest = np.concatenate([i * K + np.arange(k, dtype=np.int64) for i, k in enumerate(ks)])
+        P = int(self.detector.MAX_FRAMES_PER_PASS)
+        parts = []
+        with torch.no_grad(), torch.cuda.device(self.device):
+            slots, lens = self._ids_and_lengths(idx, ks, K)
+            rows = self._upload(dest)
+            for p0 in range(0, len(flat), P):
+                parts.append(self.detector._enqueue_padded(flat[p0:p0 + P], self.device))
+            md = int(parts[0][0].shape[1])
+            if any(int(p[0].shape[1]) != md for p in parts):
+                raise RuntimeError("the detector's passes disagree on the padded detection count")
+            det = []
+            for q in range(4):
+                src = torch.cat([p[q] for p in parts])
+                out = torch.zeros((n * K,) + tuple(src.shape[1:]), dtype=src.dtype, device=self.device)
+                out.index_copy_(0, rows, src)
+                det.append(out.view((n, K) + tuple(src.shape[1:])))
+            boxes, scores, labels, n_det = det
+            x = torch.empty((n, K, MAX_OBJECTS, self.n_tracks), dtype=torch.float32, device=self.device)
+            self._encode_into(x, slots, boxes, scores, labels, n_det, lens)
+        return self._advance(slots, x, (boxes, scores, labels, n_det), lens)

@@ -22,6 +22,11 @@ variants), through opseq_stream_step_f32 and the stacked launch chain's own step
     h_n, c_n = streams.get_state(ids)              # [L, n, H] each (nn.LSTM's h_n / c_n)
     streams.set_state(ids, h_n, c_n)
 
+Both pools take per-stream frame counts (`step(ids, boxes, lengths)`, lengths [n] in 0..k): stream i consumes
+boxes[i, :lengths[i]], the rest of its row is padding that never reaches the state, and its outputs there are +0.0
+(opnet_stream_step_ragged_f32 / opseq_stream_step_ragged_f32).  One call then serves a tick in which the streams have
+different numbers of new frames, with the bits of the uniform call over the same streams on every valid frame.
+
 TransformerLstm is not streamed: its encoder attends over the whole sequence, so a frame's output depends on later frames.
 """
 from __future__ import annotations
@@ -85,6 +90,24 @@ class StreamSlots:
         return idx
 
 
+def check_lengths(lengths, n: int, k: int) -> np.ndarray:
+    """host per-stream frame counts as int32 [n], or an exception: wrong shape, not integers, or outside [0, k]"""
+    a = np.asarray(lengths)
+    if a.shape != (n,):
+        raise ValueError(f"lengths must be [n={n}], got shape {a.shape}")
+    if a.dtype.kind not in "iu":
+        raise TypeError(f"lengths must be integers, got {a.dtype}")
+    if n and (int(a.min()) < 0 or int(a.max()) > k):
+        raise ValueError(f"lengths must lie in [0, k={k}], got [{int(a.min())}, {int(a.max())}]")
+    return a.astype(np.int32)
+
+
+def upload_async(a: np.ndarray, device) -> torch.Tensor:
+    """a host array on the device without a host sync: a fresh pinned copy, then an asynchronous copy on the current
+    stream (the caching host allocator keeps the pinned block until that copy has run)"""
+    return torch.from_numpy(np.ascontiguousarray(a)).pin_memory().to(device, non_blocking=True)
+
+
 class _StreamPool:
     """What every stream pool shares: the model's ROCm device, the slot bookkeeping, the state pool (one row of `row`
     floats per slot, zero at open) and the per-(n, k, stream) workspaces."""
@@ -121,6 +144,23 @@ class _StreamPool:
 
     def close(self, ids: Sequence[int]) -> None:
         self.slots.close(ids)
+
+    def _device_ids(self, idx: np.ndarray, lengths, k: int):
+        """(slots, lengths) on the device for a call of k frames: the uniform call (lengths None) uploads the slot ids as
+        it always has; host lengths are checked and go up with the ids in one pinned copy; an int32 device tensor [n] is
+        taken as is (its values are clamped to [0, k] by the kernels).  No host sync on the ragged routes."""
+        n = idx.size
+        with torch.cuda.device(self.device):
+            if lengths is None:
+                return torch.from_numpy(idx.astype(np.int32)).to(self.device), None   # one small H2D copy on this stream
+            if isinstance(lengths, torch.Tensor) and lengths.is_cuda:
+                if lengths.device != self.device:
+                    raise ValueError(f"lengths are on {lengths.device}, the stream pool on {self.device}")
+                if lengths.dtype != torch.int32 or tuple(lengths.shape) != (n,):
+                    raise ValueError(f"device lengths must be int32 [n={n}], got {lengths.dtype} {tuple(lengths.shape)}")
+                return upload_async(idx.astype(np.int32), self.device), lengths.contiguous()
+            both = upload_async(np.concatenate([idx.astype(np.int32), check_lengths(lengths, n, k)]), self.device)
+            return both[:n], both[n:]
 
 
 class OPNetStreams(_StreamPool):
@@ -183,9 +223,10 @@ class OPNetStreams(_StreamPool):
                 self.state.index_copy_(0, dst, torch.cat(cols, dim=1))
 
     # -- frames -------------------------------------------------------------------------------
-    def step(self, ids: Sequence[int], boxes: torch.Tensor):
+    def step(self, ids: Sequence[int], boxes: torch.Tensor, lengths=None):
         """advance the streams `ids` by k frames: boxes [n, k, 15, 6] (row i belongs to ids[i]) -> (y [n, k, 4],
-        logits [n, 15, k]), the outputs of those frames"""
+        logits [n, 15, k]), the outputs of those frames.  lengths ([n] ints in 0..k, on the host or an int32 device
+        tensor): stream i advances by its first lengths[i] frames only; y / logits are +0.0 on the others."""
         if not isinstance(boxes, torch.Tensor) or not boxes.is_cuda:
             raise RuntimeError("OPNetStreams.step runs on MI355X only: `boxes` must be a tensor on a ROCm device")
         if boxes.device != self.device:
@@ -194,13 +235,12 @@ class OPNetStreams(_StreamPool):
         n = idx.size
         if boxes.dim() != 4 or boxes.shape[0] != n or boxes.shape[2] != 15 or boxes.shape[3] != 6 or boxes.shape[1] < 1:
             raise ValueError(f"boxes must be [n={n}, k>=1, 15, 6], got {tuple(boxes.shape)}")
-        with torch.cuda.device(self.device):
-            slots = torch.from_numpy(idx.astype(np.int32)).to(self.device)      # one small H2D copy on this stream
-        return self._step_slots(slots, boxes)
+        slots, lens = self._device_ids(idx, lengths, int(boxes.shape[1]))
+        return self._step_slots(slots, boxes, lens)
 
-    def _step_slots(self, slots: torch.Tensor, boxes: torch.Tensor):
-        """step with the slot ids already on the device (int32 [n], checked by the caller) and boxes [n, k, 15, 6]
-        checked: no host synchronisation"""
+    def _step_slots(self, slots: torch.Tensor, boxes: torch.Tensor, lengths: Optional[torch.Tensor] = None):
+        """step with the slot ids (and the lengths of a ragged call) already on the device (int32 [n], checked by the
+        caller) and boxes [n, k, 15, 6] checked: no host synchronisation"""
         n, k = int(boxes.shape[0]), int(boxes.shape[1])
         lib = _lib.load()
         with torch.no_grad(), torch.cuda.device(self.device):
@@ -210,10 +250,17 @@ class OPNetStreams(_StreamPool):
             ws = self._ws.get(stream, (n, k), self.device, (lib.opnet_stream_workspace_bytes, n, k, self.H1, self.H2))
             y = torch.empty((n, k, 4), dtype=torch.float32, device=self.device)
             logits = torch.empty((n, 15, k), dtype=torch.float32, device=self.device)
-            rc = lib.opnet_stream_step_f32(boxes.data_ptr(), slots.data_ptr(), self.state.data_ptr(), packed.data_ptr(),
-                                           y.data_ptr(), logits.data_ptr(), ws.data_ptr(), ws.numel(), n, k, self.capacity,
-                                           self.H1, self.H2, self._mlp, stream)
-            _lib.check(rc, "opnet_stream_step_f32")
+            if lengths is None:
+                rc = lib.opnet_stream_step_f32(boxes.data_ptr(), slots.data_ptr(), self.state.data_ptr(), packed.data_ptr(),
+                                               y.data_ptr(), logits.data_ptr(), ws.data_ptr(), ws.numel(), n, k,
+                                               self.capacity, self.H1, self.H2, self._mlp, stream)
+                _lib.check(rc, "opnet_stream_step_f32")
+            else:
+                rc = lib.opnet_stream_step_ragged_f32(boxes.data_ptr(), slots.data_ptr(), lengths.data_ptr(),
+                                                      self.state.data_ptr(), packed.data_ptr(), y.data_ptr(),
+                                                      logits.data_ptr(), ws.data_ptr(), ws.numel(), n, k, self.capacity,
+                                                      self.H1, self.H2, self._mlp, stream)
+                _lib.check(rc, "opnet_stream_step_ragged_f32")
         return y, logits
 
 
@@ -261,9 +308,10 @@ class LstmStackStreams(_StreamPool):
             self.state.index_copy_(0, torch.from_numpy(idx).to(self.device), rows)
 
     # -- frames -------------------------------------------------------------------------------
-    def step(self, ids: Sequence[int], x: torch.Tensor) -> torch.Tensor:
+    def step(self, ids: Sequence[int], x: torch.Tensor, lengths=None) -> torch.Tensor:
         """advance the streams `ids` by k frames: x [n, k, 15, 5] (row i belongs to ids[i]) -> y [n, k, 4], the outputs
-        of those frames"""
+        of those frames.  lengths ([n] ints in 0..k, on the host or an int32 device tensor): stream i advances by its
+        first lengths[i] frames only; y is +0.0 on the others."""
         if not isinstance(x, torch.Tensor) or not x.is_cuda:
             raise RuntimeError("LstmStackStreams.step runs on MI355X only: `x` must be a tensor on a ROCm device")
         if x.device != self.device:
@@ -273,13 +321,12 @@ class LstmStackStreams(_StreamPool):
         S, F = self.slots_per_frame, self.features
         if x.dim() != 4 or x.shape[0] != n or x.shape[2] != S or x.shape[3] != F or x.shape[1] < 1:
             raise ValueError(f"x must be [n={n}, k>=1, {S}, {F}], got {tuple(x.shape)}")
-        with torch.cuda.device(self.device):
-            slots = torch.from_numpy(idx.astype(np.int32)).to(self.device)      # one small H2D copy on this stream
-        return self._step_slots(slots, x)
+        slots, lens = self._device_ids(idx, lengths, int(x.shape[1]))
+        return self._step_slots(slots, x, lens)
 
-    def _step_slots(self, slots: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
-        """step with the slot ids already on the device (int32 [n], checked by the caller) and x [n, k, 15, 5] checked:
-        no host synchronisation"""
+    def _step_slots(self, slots: torch.Tensor, x: torch.Tensor, lengths: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """step with the slot ids (and the lengths of a ragged call) already on the device (int32 [n], checked by the
+        caller) and x [n, k, 15, 5] checked: no host synchronisation"""
         n, k = int(x.shape[0]), int(x.shape[1])
         S = self.slots_per_frame
         m = self.model
@@ -297,8 +344,14 @@ class LstmStackStreams(_StreamPool):
             packed = m._runner._packed_weights(m._runner.weights(m.video_LSTM, m.predictions_layer), self.device, stream)
             ws = self._ws.get(stream, (n, k), self.device, (lib.opseq_stream_workspace_bytes, n, k, self.L, self.KX, self.H))
             y = torch.empty((n, k, 4), dtype=torch.float32, device=self.device)
-            rc = lib.opseq_stream_step_f32(feats.data_ptr(), slots.data_ptr(), self.state.data_ptr(), packed.data_ptr(),
-                                           y.data_ptr(), ws.data_ptr(), ws.numel(), n, k, self.capacity, self.L, self.KX,
-                                           self.H, stream)
-            _lib.check(rc, "opseq_stream_step_f32")
+            if lengths is None:
+                rc = lib.opseq_stream_step_f32(feats.data_ptr(), slots.data_ptr(), self.state.data_ptr(), packed.data_ptr(),
+                                               y.data_ptr(), ws.data_ptr(), ws.numel(), n, k, self.capacity, self.L, self.KX,
+                                               self.H, stream)
+                _lib.check(rc, "opseq_stream_step_f32")
+            else:
+                rc = lib.opseq_stream_step_ragged_f32(feats.data_ptr(), slots.data_ptr(), lengths.data_ptr(),
+                                                      self.state.data_ptr(), packed.data_ptr(), y.data_ptr(), ws.data_ptr(),
+                                                      ws.numel(), n, k, self.capacity, self.L, self.KX, self.H, stream)
+                _lib.check(rc, "opseq_stream_step_ragged_f32")
         return y
