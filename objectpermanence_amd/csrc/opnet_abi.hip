@@ -167,6 +167,8 @@ static void launch_attention(const float *qkv, float *att, int S, int nseg, int 
 }
 
 static inline bool aligned16(const void *p) { return (((uintptr_t)p) & 15u) == 0; }
+// blocks of 256 threads for a grid-stride loop over n items, at most cap of them
+static unsigned ew_blocks(long n, long cap = 16384) { return (unsigned)((n + 255) / 256 > cap ? cap : (n + 255) / 256); }
 
 extern "C" int opnet_hip_abi_version(void) { return OPNET_HIP_ABI_VERSION; }
 extern "C" const char *opnet_last_error(void) { return g_err; }
@@ -192,13 +194,26 @@ static bool step_is_preload(const StepArgs &a)
     return step_is_nw8(a) && !a.mlp && !a.train && env_int("OPNET_PRELOAD", 1) != 0;
 }
 static int step_threads(const StepArgs &a) { return step_is_nw8(a) ? 8 * 64 : OPNET_THREADS; }
-static opnet_step_fn step_kernel(const StepArgs &a)
+// The form of the step kernel for a shape, decided once for both families (opnet_step*, lstm_stack_step*) and both
+// instantiations: step_kernel / stack_step_kernel map it to the uniform kernel, step_kernel_ragged / stack_step_kernel_ragged
+// (opnet_stream_abi.hip, seq_stream_abi.hip) to the ragged one, so a ragged call runs the form of the uniform call of the
+// same shape.  The values index the kernel tables.
+enum StepForm { STEP_CH8, STEP_CH4, STEP_NW8, STEP_WIDE_CH8, STEP_WIDE_CH4 };
+static bool step_small_chunks(int RB)
 {
     const char *force = getenv("OPNET_STEP_CH");          // "4" / "8": measurement override (4-wave kernels)
-    const bool small_chunks = force ? atoi(force) == 4 : a.RB >= 2;
-    if (step_is_wide(a)) return small_chunks ? opnet_step_wide<4> : opnet_step_wide<8>;
-    if (step_is_nw8(a)) return opnet_step<4, 8>;
-    return small_chunks ? opnet_step<4> : opnet_step<8>;
+    return force ? atoi(force) == 4 : RB >= 2;
+}
+static StepForm step_form(const StepArgs &a)
+{
+    if (step_is_wide(a)) return step_small_chunks(a.RB) ? STEP_WIDE_CH4 : STEP_WIDE_CH8;
+    if (step_is_nw8(a)) return STEP_NW8;
+    return step_small_chunks(a.RB) ? STEP_CH4 : STEP_CH8;
+}
+static opnet_step_fn step_kernel(const StepArgs &a)
+{
+    static const opnet_step_fn k[] = {opnet_step<8>, opnet_step<4>, opnet_step<4, 8>, opnet_step_wide<8>, opnet_step_wide<4>};
+    return k[step_form(a)];
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1741,11 +1756,16 @@ static bool stack_hoists_input(int KX, int H) { return (KX & 15) == 0 && KX >= 2
 typedef void (*stack_step_fn)(const StackArgs, const int);
 static bool stack_is_nw8(int RB) { return !getenv("OPNET_STEP_CH") && RB <= env_int("OPNET_NW8_MAX_RB", 1); }
 static int stack_step_threads(int RB) { return stack_is_nw8(RB) ? 8 * 64 : OPNET_THREADS; }
+// the stacked step's form (step_form): no wide form
+static StepForm stack_step_form(int RB)
+{
+    if (stack_is_nw8(RB)) return STEP_NW8;
+    return step_small_chunks(RB) ? STEP_CH4 : STEP_CH8;
+}
 static stack_step_fn stack_step_kernel(int RB)
 {
-    const char *force = getenv("OPNET_STEP_CH");          // "4" / "8": measurement override (4-wave kernels)
-    if (stack_is_nw8(RB)) return lstm_stack_step<4, 8>;
-    return (force ? atoi(force) == 4 : RB >= 2) ? lstm_stack_step<4> : lstm_stack_step<8>;
+    static const stack_step_fn k[] = {lstm_stack_step<8>, lstm_stack_step<4>, lstm_stack_step<4, 8>};
+    return k[stack_step_form(RB)];
 }
 
 struct StackPackedLayout { size_t layer[SEQ_MAX_LAYERS], head, wih0g, total; int nhx[SEQ_MAX_LAYERS]; };
@@ -3039,8 +3059,6 @@ extern "C" int opseq_encoder_layer_batched_f32(float *z, const float *in_w, cons
 // ------------------------------------------------------------------------------------------------
 // detector backbone primitives (NHWC fp32)
 // ------------------------------------------------------------------------------------------------
-static unsigned ew_blocks(long n) { return (unsigned)((n + 255) / 256 > 16384 ? 16384 : (n + 255) / 256); }
-
 static int conv_args(ConvArgs *a, const float *x, const float *w, const float *bias, const float *residual, float *y, int N, int H, int W,
                      int Cin, int Cout, int KH, int KW, int stride, int pad, int KP, int relu)
 {

@@ -372,25 +372,35 @@ __device__ __forceinline__ float lstm_cell(float gi, float gf, float gg, float g
 // too large length acts as 0 or T): no access depends on it.
 __device__ __forceinline__ bool column_live(const int32_t *len, int B, long b, int t) { return b >= B || t < len[b]; }
 
-// lstm_cell_g for the ragged step kernels, with the contractions the compiler makes in the uniform kernels written out:
-// c = fma(f, c_old, i * g) and tanh's 1 - 2 r = fma(-2, r, 1).  Left to itself, the compiler pairs f * c_old and i * g
-// into one packed multiply once c feeds the ragged select, and the sum then rounds differently.
+// The cell update of the step kernels (opnet_step*, lstm_stack_step*), uniform and ragged: gates -> h, c to *c_out, the
+// post-activation gates to *gates.  The contractions are written out - c = fma(c_old, f, i * g), tanh's 1 - 2 r =
+// fma(-2, r, 1) - because the compiler, left to itself, pairs f * c_old and i * g into one packed multiply once c feeds the
+// ragged select, and the sum then rounds differently.  Written out, both forms round as lstm_cell_g does, and the uniform
+// kernels compile to the very instructions lstm_cell_g gave them (the c_old, f order included).  RAGGED: a frozen column
+// (live false) keeps h_old and c_old through selects, not 0/1 products - a padding frame's gates may be NaN.  lstm_cell_g
+// stays for the persistent kernels (opnet_xcd*, seq_xcd*), which have no ragged form.
 #if OPNET_FAST_GATES
 __device__ __forceinline__ float tanh_fused(float x) { return __builtin_fmaf(-2.0f, __builtin_amdgcn_rcpf(1.0f + __expf(2.0f * x)), 1.0f); }
 #else
 __device__ __forceinline__ float tanh_fused(float x) { return tanhf(x); }
 #endif
-__device__ __forceinline__ float lstm_cell_fused(float gi, float gf, float gg, float go, float c_old, float *c_out,
-                                                 float4 *gates)
+template <bool RAGGED>
+__device__ __forceinline__ float cell_step(float gi, float gf, float gg, float go, float c_old, float h_old, bool live,
+                                           float *c_out, float4 *gates)
 {
     const float i = fast_sigmoid(gi);
     const float f = fast_sigmoid(gf);
     const float g = tanh_fused(gg);
     const float o = fast_sigmoid(go);
-    const float c = __builtin_fmaf(f, c_old, i * g);
-    *c_out = c;
+    const float c = __builtin_fmaf(c_old, f, i * g);
+    const float h = o * tanh_fused(c);
     *gates = make_float4(i, f, g, o);
-    return o * tanh_fused(c);
+    if constexpr (RAGGED) {
+        *c_out = live ? c : c_old;
+        return live ? h : h_old;
+    }
+    *c_out = c;
+    return h;
 }
 
 // history slots: inference keeps two parity slots per state buffer, training keeps every step
@@ -615,16 +625,9 @@ __device__ __forceinline__ void opnet_step_body(const StepArgs &a, const int s, 
                     xs = fmaf(w1.y, xb.y, xs);
                     g[r] = part_sum<NW>(part, half * 4 + r, el) + xs;
                 }
-                float c = c_old;
+                float c;
                 float4 gs;
-                float h;
-                if constexpr (RAGGED) {   // selects, not 0/1 products: a padding frame's gates may be NaN
-                    h = lstm_cell_fused(g[0], g[1], g[2], g[3], c_old, &c, &gs);
-                    h = live ? h : h_old;
-                    c = live ? c : c_old;
-                } else {
-                    h = lstm_cell_g(g[0], g[1], g[2], g[3], &c, &gs);
-                }
+                const float h = cell_step<RAGGED>(g[0], g[1], g[2], g[3], c_old, h_old, live, &c, &gs);
                 a.c2[((cslot_out(a, t) * a.RB + rb) * H2 + unit) * 32 + clip] = c;
                 if (a.train) a.g2save[(((long)t * a.RB + rb) * H2 + unit) * 32 + clip] = gs;
                 float *hout = (float *)(a.h2buf + (slot_out(a, t) * a.RB + rb) * (H2 * 8));
@@ -659,18 +662,11 @@ __device__ __forceinline__ void opnet_step_body(const StepArgs &a, const int s, 
             __syncthreads();
             TRACE_STAMP(4);
             if (tid < 128) {
-                float c = c_old;
+                float c;
                 float4 gs;
-                float h;
-                if constexpr (RAGGED) {
-                    h = lstm_cell_fused(part_sum<NW>(part, half * 4 + 0, el), part_sum<NW>(part, half * 4 + 1, el),
-                                        part_sum<NW>(part, half * 4 + 2, el), part_sum<NW>(part, half * 4 + 3, el), c_old, &c, &gs);
-                    h = live ? h : h_old;
-                    c = live ? c : c_old;
-                } else {
-                    h = lstm_cell_g(part_sum<NW>(part, half * 4 + 0, el), part_sum<NW>(part, half * 4 + 1, el),
-                                    part_sum<NW>(part, half * 4 + 2, el), part_sum<NW>(part, half * 4 + 3, el), &c, &gs);
-                }
+                const float h = cell_step<RAGGED>(part_sum<NW>(part, half * 4 + 0, el), part_sum<NW>(part, half * 4 + 1, el),
+                                                  part_sum<NW>(part, half * 4 + 2, el), part_sum<NW>(part, half * 4 + 3, el),
+                                                  c_old, h_old, live, &c, &gs);
                 a.c1[((cslot_out(a, t) * a.RB + rb) * H1 + unit) * 32 + clip] = c;
                 if (a.train) a.g1save[(((long)t * a.RB + rb) * H1 + unit) * 32 + clip] = gs;
                 float *hout = (float *)(a.h1buf + (slot_out(a, t) * a.RB + rb) * (H1 * 8));
@@ -853,16 +849,9 @@ __device__ __forceinline__ void opnet_step_wide_body(const StepArgs &a, const in
                 xs = fmaf(w1.y, xb.y, xs);
                 g[r] = part_sum2(part, ereg + r, el) + xs;
             }
-            float c = c_old;
+            float c;
             float4 gs;
-            float h;
-            if constexpr (RAGGED) {
-                h = lstm_cell_fused(g[0], g[1], g[2], g[3], c_old, &c, &gs);
-                h = live ? h : h_old;
-                c = live ? c : c_old;
-            } else {
-                h = lstm_cell_g(g[0], g[1], g[2], g[3], &c, &gs);
-            }
+            const float h = cell_step<RAGGED>(g[0], g[1], g[2], g[3], c_old, h_old, live, &c, &gs);
             a.c2[((cslot_out(a, t) * a.RB + rb) * H2 + unit) * 32 + clip] = c;
             if (a.train) a.g2save[(((long)t * a.RB + rb) * H2 + unit) * 32 + clip] = gs;
             float *hout = (float *)(a.h2buf + (slot_out(a, t) * a.RB + rb) * (H2 * 8));
@@ -895,18 +884,11 @@ __device__ __forceinline__ void opnet_step_wide_body(const StepArgs &a, const in
             }
             gemm32_rb(a0, a1, a_qb, A0, A1, xsrc, OPNET_KXQ / 4, hprev, ks, part, a.B - rb * 32 > 16);
             __syncthreads();
-            float c = c_old;
+            float c;
             float4 gs;
-            float h;
-            if constexpr (RAGGED) {
-                h = lstm_cell_fused(part_sum2(part, ereg + 0, el), part_sum2(part, ereg + 1, el),
-                                    part_sum2(part, ereg + 2, el), part_sum2(part, ereg + 3, el), c_old, &c, &gs);
-                h = live ? h : h_old;
-                c = live ? c : c_old;
-            } else {
-                h = lstm_cell_g(part_sum2(part, ereg + 0, el), part_sum2(part, ereg + 1, el),
-                                part_sum2(part, ereg + 2, el), part_sum2(part, ereg + 3, el), &c, &gs);
-            }
+            const float h = cell_step<RAGGED>(part_sum2(part, ereg + 0, el), part_sum2(part, ereg + 1, el),
+                                              part_sum2(part, ereg + 2, el), part_sum2(part, ereg + 3, el), c_old, h_old, live,
+                                              &c, &gs);
             a.c1[((cslot_out(a, t) * a.RB + rb) * H1 + unit) * 32 + clip] = c;
             if (a.train) a.g1save[(((long)t * a.RB + rb) * H1 + unit) * 32 + clip] = gs;
             float *hout = (float *)(a.h1buf + (slot_out(a, t) * a.RB + rb) * (H1 * 8));

@@ -1,6 +1,6 @@
 // opnet_stream_abi.hip - host side of the stateful OPNet streams (C ABI: opnet_stream_*; kernels in opnet_stream_kernels.hip).
-// Included by opnet_abi.hip (one translation unit: it uses that file's fail / HIP_TRY / check_dims / aligned16 and the launch
-// chain's step_kernel / step_grid / step_threads).
+// Included by opnet_abi.hip (one translation unit: it uses that file's fail / HIP_TRY / check_dims / aligned16 / ew_blocks and
+// the launch chain's step_form / step_kernel / step_grid / step_threads).
 #pragma once
 
 extern "C" size_t opnet_stream_state_floats(int H1, int H2)
@@ -22,15 +22,13 @@ extern "C" size_t opnet_stream_workspace_bytes(int n, int k, int H1, int H2)
 typedef void (*opnet_step_ragged_fn)(const StepArgs, const int, const int32_t *);
 static opnet_step_ragged_fn step_kernel_ragged(const StepArgs &a)
 {
-    const char *force = getenv("OPNET_STEP_CH");
-    const bool small_chunks = force ? atoi(force) == 4 : a.RB >= 2;
-    if (step_is_wide(a)) return small_chunks ? opnet_step_wide_ragged<4> : opnet_step_wide_ragged<8>;
-    if (step_is_nw8(a)) return opnet_step_ragged<4, 8>;
-    return small_chunks ? opnet_step_ragged<4> : opnet_step_ragged<8>;
+    static const opnet_step_ragged_fn k[] = {opnet_step_ragged<8>, opnet_step_ragged<4>, opnet_step_ragged<4, 8>,
+                                             opnet_step_wide_ragged<8>, opnet_step_wide_ragged<4>};
+    return k[step_form(a)];
 }
 
 // prologue -> k + 3 step launches -> write-back: k + 5 dependent launches on `stream`, no host synchronisation.  lengths
-// (device [n], or null for the uniform call) selects the ragged step and write-back kernels.
+// (device [n], or null for the uniform call) selects the ragged step kernel and is the write-back's len.
 static int opnet_stream_step(const float *boxes, const int32_t *slots, const int32_t *lengths, float *state,
                              const float *packed, float *y, float *logits, void *workspace, size_t workspace_bytes, int n,
                              int k, int capacity, int H1, int H2, int mlp, void *stream)
@@ -58,13 +56,12 @@ static int opnet_stream_step(const float *boxes, const int32_t *slots, const int
     s.logits = logits;
     s.xp = (float4 *)((char *)workspace + W.xp);
     s.capacity = capacity;
+    s.len = lengths;
     const StepArgs &a = s.a;
     hipStream_t st = (hipStream_t)stream;
 
     // gather workgroups per row block: one work item per (unit quad, clip), up to 256 a thread
-    const int gather_items = (H1 + H2) / 4 * 32;
-    const int G = (gather_items + 255) / 256 < 64 ? (gather_items + 255) / 256 : 64;
-    opnet_stream_prologue<<<dim3(k + G, a.RB), 256, 0, st>>>(s);
+    opnet_stream_prologue<<<dim3(k + ew_blocks((H1 + H2) / 4 * 32, 64), a.RB), 256, 0, st>>>(s);
     // the chain's step kernel for this shape; the kernarg-preload form (opnet_step_pl) is left out: it carves its buffers
     // from the chain's own workspace, and computes the same body as opnet_step<4, 8>
     const dim3 grid = step_grid(a);
@@ -75,11 +72,8 @@ static int opnet_stream_step(const float *boxes, const int32_t *slots, const int
         const opnet_step_fn stepk = step_kernel(a);
         for (int t = 0; t < k + 3; ++t) stepk<<<grid, step_threads(a), 0, st>>>(a, t);
     }
-    const long items = (long)a.B * OPNET_SLOTS * k > (long)a.RB * 32 * (H1 + H2) / 4 ? (long)a.B * OPNET_SLOTS * k
-                                                                                     : (long)a.RB * 32 * (H1 + H2) / 4;
-    const unsigned wb = (unsigned)((items + 255) / 256 > 1024 ? 1024 : (items + 255) / 256);
-    if (lengths) opnet_stream_writeback_ragged<<<wb, 256, 0, st>>>(s, lengths);
-    else opnet_stream_writeback<<<wb, 256, 0, st>>>(s);
+    const long outputs = (long)a.B * OPNET_SLOTS * k, states = (long)a.RB * 32 * (H1 + H2) / 4;
+    opnet_stream_writeback<<<ew_blocks(outputs > states ? outputs : states, 1024), 256, 0, st>>>(s);
     HIP_TRY(hipGetLastError());
     return OPNET_OK;
 }

@@ -10,7 +10,8 @@
 //   write-back : the rings after step k-1 (slot_out / cslot_out) -> the pool rows, and the staging buffers -> the
 //                caller's y / logits, as opnet_copy_out.
 // Ragged calls (opnet_stream_step_ragged_f32) run the step kernel's ragged form, where stream b's column freezes from frame
-// len[b] on, so the state copy is the same; their write-back writes +0.0 to y / logits at frames t >= len[b].
+// len[b] on, so the state copy is the same; the write-back then writes +0.0 to y / logits at frames t >= len[b] (StreamArgs
+// len; null for uniform calls).
 // Gather and write-back are plain fp32 copies, so a clip's frames see exactly the arithmetic of the whole-clip chain
 // whatever the chunking.  OPNetLstmMlp (a.mlp) has no LSTM2 state: its h2 / c2 columns are neither read nor written.
 #pragma once
@@ -24,6 +25,7 @@ struct StreamArgs {
     float *logits;           // [n][15][k]
     float4 *xp;              // the packed LSTM1 input of the workspace (a.xp, writable)
     long capacity;
+    const int32_t *len;      // [n] frames per stream (ragged calls), or null: k each
 };
 
 __device__ __forceinline__ const float *stream_row(const StreamArgs &s, int b)
@@ -76,46 +78,17 @@ __global__ void __launch_bounds__(256) opnet_stream_prologue(const StreamArgs s)
     }
 }
 
-// a stream's frame count in a ragged call, clamped to [0, k]: the kernels cannot trust a device array the host never saw
-__device__ __forceinline__ int stream_len(const int32_t *len, long b, int k) { return min(max(len[b], 0), k); }
-
-// 1-D grid-stride: the final state of every stream (after LSTM1 / LSTM2 step k-1) -> its pool row, then y and logits
-__global__ void __launch_bounds__(256) opnet_stream_writeback(const StreamArgs s)
+// element i of a [n][.. per ..] output, at frame i % k of stream i / per, keeps its value: always in a uniform call (len
+// null), for the first len[b] frames of a ragged one (clamped to [0, k]: the kernels cannot trust a device array the host
+// never saw); otherwise it is written as +0.0
+__device__ __forceinline__ bool frame_kept(const int32_t *len, long i, long per, int k)
 {
-    const StepArgs &a = s.a;
-    const int k = a.T;
-    const int Q1 = a.H1 >> 2, Q = a.mlp ? Q1 : Q1 + (a.H2 >> 2);
-    const long stride = (long)gridDim.x * blockDim.x;
-    const long i0 = blockIdx.x * (long)blockDim.x + threadIdx.x;
-    const long nst = (long)a.RB * Q * 32;
-    for (long j = i0; j < nst; j += stride) {
-        const int clip = j & 31;
-        const long rq = j >> 5;
-        const int q = rq % Q;
-        const int rb = rq / Q;
-        const int b = rb * 32 + clip;
-        if (b >= a.B) continue;
-        float *row = (float *)stream_row(s, b);
-        if (!row) continue;
-        const bool l1 = q < Q1;
-        const int H = l1 ? a.H1 : a.H2;
-        const int u4 = l1 ? q : q - Q1;
-        const float4 *hb = l1 ? a.h1buf : a.h2buf;
-        const float *cb = l1 ? a.c1 : a.c2;
-        const float4 h = hb[((slot_out(a, k - 1) * a.RB + rb) * (H >> 2) + u4) * 32 + clip];
-        const float *cc = cb + ((cslot_out(a, k - 1) * a.RB + rb) * H + 4 * u4) * 32 + clip;
-        row += l1 ? 0 : 2 * a.H1;
-        *(float4 *)(row + 4 * u4) = h;
-        *(float4 *)(row + H + 4 * u4) = make_float4(cc[0], cc[32], cc[64], cc[96]);
-    }
-    const long ny = (long)a.B * k;                   // float4 units
-    const long nl = (long)a.B * OPNET_SLOTS_ * k;    // floats
-    for (long i = i0; i < ny; i += stride) ((float4 *)s.y)[i] = a.ystage[i];
-    for (long i = i0; i < nl; i += stride) s.logits[i] = a.lgstage[i];
+    return !len || (int)(i % k) < min(max(len[i / per], 0), k);
 }
 
-// the same with +0.0 at frames t >= len[b] (ragged calls)
-__global__ void __launch_bounds__(256) opnet_stream_writeback_ragged(const StreamArgs s, const int32_t *len)
+// 1-D grid-stride: the final state of every stream (after LSTM1 / LSTM2 step k-1) -> its pool row, then y and logits
+// (+0.0 at the frames frame_kept drops)
+__global__ void __launch_bounds__(256) opnet_stream_writeback(const StreamArgs s)
 {
     const StepArgs &a = s.a;
     const int k = a.T;
@@ -147,8 +120,7 @@ __global__ void __launch_bounds__(256) opnet_stream_writeback_ragged(const Strea
     const long nl = (long)a.B * OPNET_SLOTS_ * k;    // floats
     for (long i = i0; i < ny; i += stride) {
         const float4 v = a.ystage[i];
-        ((float4 *)s.y)[i] = (int)(i % k) < stream_len(len, i / k, k) ? v : make_float4(0.f, 0.f, 0.f, 0.f);
+        ((float4 *)s.y)[i] = frame_kept(s.len, i, k, k) ? v : make_float4(0.f, 0.f, 0.f, 0.f);
     }
-    for (long i = i0; i < nl; i += stride)
-        s.logits[i] = (int)(i % k) < stream_len(len, i / ((long)OPNET_SLOTS_ * k), k) ? a.lgstage[i] : 0.f;
+    for (long i = i0; i < nl; i += stride) s.logits[i] = frame_kept(s.len, i, (long)OPNET_SLOTS_ * k, k) ? a.lgstage[i] : 0.f;
 }

@@ -127,18 +127,11 @@ __device__ __forceinline__ void lstm_stack_step_body(const StackArgs &a, const i
             gemm16_rb(a0, a_qb, A, xseg, nhx, hprev, ks, part, s, a.B - rb * 32 > 16);
             __syncthreads();
             if (tid < 128) {
-                float c = c_old;
+                float c;
                 float4 gs;
-                float h;
-                if constexpr (RAGGED) {   // selects, not 0/1 products: a padding frame's gates may be NaN
-                    h = lstm_cell_fused(part_sum<NW>(part, half * 4 + 0, el) + xg.x, part_sum<NW>(part, half * 4 + 1, el) + xg.y,
-                                        part_sum<NW>(part, half * 4 + 2, el) + xg.z, part_sum<NW>(part, half * 4 + 3, el) + xg.w, c_old, &c, &gs);
-                    h = live ? h : h_old;
-                    c = live ? c : c_old;
-                } else {
-                    h = lstm_cell_g(part_sum<NW>(part, half * 4 + 0, el) + xg.x, part_sum<NW>(part, half * 4 + 1, el) + xg.y,
-                                    part_sum<NW>(part, half * 4 + 2, el) + xg.z, part_sum<NW>(part, half * 4 + 3, el) + xg.w, &c, &gs);
-                }
+                const float h = cell_step<RAGGED>(part_sum<NW>(part, half * 4 + 0, el) + xg.x, part_sum<NW>(part, half * 4 + 1, el) + xg.y,
+                                                  part_sum<NW>(part, half * 4 + 2, el) + xg.z, part_sum<NW>(part, half * 4 + 3, el) + xg.w,
+                                                  c_old, h_old, live, &c, &gs);
                 ly.c[((co * a.RB + rb) * H + unit) * 32 + clip] = c;
                 if (a.train) ly.gsave[(((long)t * a.RB + rb) * H + unit) * 32 + clip] = gs;
                 float *hout = (float *)(ly.hbuf + (so * a.RB + rb) * ((long)H * 8));

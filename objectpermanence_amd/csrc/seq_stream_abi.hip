@@ -1,6 +1,7 @@
 // seq_stream_abi.hip - host side of the stateful stacked-LSTM streams (C ABI: opseq_stream_*; kernels in
 // seq_stream_kernels.hip).  Included by opnet_abi.hip (one translation unit: it uses that file's fail / HIP_TRY / env_int /
-// aligned16 and the launch chain's check_stack / stack_args_inference / stack_hoisted_input_tiled / stack_step_kernel).
+// aligned16 / ew_blocks and the launch chain's check_stack / stack_args_inference / stack_hoisted_input_tiled /
+// stack_step_form / stack_step_kernel).
 #pragma once
 
 // The skinny input product computes every 16-clip fragment of every frame that holds a live stream: k * ceil(n / 16) * 16
@@ -35,9 +36,8 @@ static void seq_stream_input_product(const float *x, const float *packed, float4
 typedef void (*stack_step_ragged_fn)(const StackArgs, const int, const int32_t *);
 static stack_step_ragged_fn stack_step_kernel_ragged(int RB)
 {
-    const char *force = getenv("OPNET_STEP_CH");
-    if (stack_is_nw8(RB)) return lstm_stack_step_ragged<4, 8>;
-    return (force ? atoi(force) == 4 : RB >= 2) ? lstm_stack_step_ragged<4> : lstm_stack_step_ragged<8>;
+    static const stack_step_ragged_fn k[] = {lstm_stack_step_ragged<8>, lstm_stack_step_ragged<4>, lstm_stack_step_ragged<4, 8>};
+    return k[stack_step_form(RB)];
 }
 
 static bool seq_stream_takes_skinny(int n, int k)
@@ -67,7 +67,8 @@ extern "C" size_t opseq_stream_workspace_bytes(int n, int k, int L, int KX, int 
 }
 
 // [hoisted input product] -> prologue -> k + 2L - 1 step launches -> write-back, dependent launches on `stream`, no host
-// synchronisation.  lengths (device [n], or null for the uniform call) selects the ragged step and write-back kernels.
+// synchronisation.  lengths (device [n], or null for the uniform call) selects the ragged step kernel and is the
+// write-back's len.
 static int opseq_stream_step(const float *x, const int32_t *slots, const int32_t *lengths, float *state, const float *packed,
                              float *y, void *workspace, size_t workspace_bytes, int n, int k, int capacity, int L, int KX,
                              int H, void *stream)
@@ -95,15 +96,14 @@ static int opseq_stream_step(const float *x, const int32_t *slots, const int32_t
     s.KX = KX;
     s.KQ = hoist ? 0 : stack_packed_layout(L, KX, H).nhx[0] * 4;
     s.capacity = capacity;
+    s.len = lengths;
     const StackArgs &a = s.a;
     hipStream_t st = (hipStream_t)stream;
 
     if (hoist)
         seq_stream_input_product(x, packed, (float4 *)(w + W.xg), w, n, k, L, KX, H, seq_stream_takes_skinny(n, k), st);
     // gather workgroups per row block: one work item per (layer, unit quad, clip), up to 256 a thread
-    const int gather_items = L * (H / 4) * 32;
-    const int G = (gather_items + 255) / 256 < 64 ? (gather_items + 255) / 256 : 64;
-    seq_stream_prologue<<<dim3((hoist ? 0 : k) + G, a.RB), 256, 0, st>>>(s);
+    seq_stream_prologue<<<dim3((hoist ? 0 : k) + ew_blocks(L * (H / 4) * 32, 64), a.RB), 256, 0, st>>>(s);
     if (lengths) {
         const stack_step_ragged_fn stepk = stack_step_kernel_ragged(a.RB);
         for (int t = 0; t < k + 2 * L - 1; ++t) stepk<<<grid, stack_step_threads(a.RB), 0, st>>>(a, t, lengths);
@@ -111,10 +111,8 @@ static int opseq_stream_step(const float *x, const int32_t *slots, const int32_t
         const stack_step_fn stepk = stack_step_kernel(a.RB);
         for (int t = 0; t < k + 2 * L - 1; ++t) stepk<<<grid, stack_step_threads(a.RB), 0, st>>>(a, t);
     }
-    const long items = (long)n * k > (long)a.RB * 32 * L * (H / 4) ? (long)n * k : (long)a.RB * 32 * L * (H / 4);
-    const unsigned wb = (unsigned)((items + 255) / 256 > 1024 ? 1024 : (items + 255) / 256);
-    if (lengths) seq_stream_writeback_ragged<<<wb, 256, 0, st>>>(s, lengths);
-    else seq_stream_writeback<<<wb, 256, 0, st>>>(s);
+    const long outputs = (long)n * k, states = (long)a.RB * 32 * L * (H / 4);
+    seq_stream_writeback<<<ew_blocks(outputs > states ? outputs : states, 1024), 256, 0, st>>>(s);
     HIP_TRY(hipGetLastError());
     return OPNET_OK;
 }

@@ -12,7 +12,8 @@
 //   skinny input : NonLinearLstm's hoisted layer-0 input product xg = x . W_ih0^T for calls with few rows, straight into
 //                  the step kernel's xg layout (see seq_stream_input_skinny).
 // Ragged calls (opseq_stream_step_ragged_f32) run lstm_stack_step_ragged, where stream b's column freezes from frame len[b]
-// on, so the state copy is the same; their write-back writes +0.0 to y at frames t >= len[b].
+// on, so the state copy is the same; the write-back then writes +0.0 to y at frames t >= len[b] (SeqStreamArgs len; null
+// for uniform calls).
 // Gather and write-back are plain fp32 copies and the skinny product does the tiled GEMM's arithmetic per element, so a
 // clip's frames see exactly the arithmetic of the whole-clip chain whatever the chunking.
 #pragma once
@@ -26,6 +27,7 @@ struct SeqStreamArgs {
     float4 *xp;              // the packed layer-0 input of the workspace (a.xp, writable); unused when hoisted
     int KX, KQ;              // layer 0's input width, and its k-quads in xp (0: hoisted, nothing to pack)
     long capacity;
+    const int32_t *len;      // [n] frames per stream (ragged calls), or null: k each
 };
 
 __device__ __forceinline__ float *seq_stream_row(const SeqStreamArgs &s, int b)
@@ -85,39 +87,9 @@ __global__ void __launch_bounds__(256) seq_stream_prologue(const SeqStreamArgs s
     }
 }
 
-// 1-D grid-stride: the final state of every stream (every layer after step k-1) -> its pool row, then ystage -> y
+// 1-D grid-stride: the final state of every stream (every layer after step k-1) -> its pool row, then ystage -> y (+0.0 at
+// the frames frame_kept drops, opnet_stream_kernels.hip)
 __global__ void __launch_bounds__(256) seq_stream_writeback(const SeqStreamArgs s)
-{
-    const StackArgs &a = s.a;
-    const int k = a.T;
-    const int H = a.layer[0].H, Q = H >> 2;
-    const long so = (k - 1) & 1;
-    const long stride = (long)gridDim.x * blockDim.x;
-    const long i0 = blockIdx.x * (long)blockDim.x + threadIdx.x;
-    const long nst = (long)a.RB * a.L * Q * 32;
-    for (long j = i0; j < nst; j += stride) {
-        const int clip = j & 31;
-        const long rq = j >> 5;
-        const int q = rq % (a.L * Q);
-        const int rb = rq / (a.L * Q);
-        const int b = rb * 32 + clip;
-        if (b >= a.B) continue;
-        float *row = seq_stream_row(s, b);
-        if (!row) continue;
-        const int l = q / Q, u4 = q - l * Q;
-        const StackLayer &ly = a.layer[l];
-        const float4 h = ly.hbuf[((so * a.RB + rb) * Q + u4) * 32 + clip];
-        const float *cc = ly.c + (((long)rb * H + 4 * u4) * 32) + clip;
-        row += 2L * l * H;
-        *(float4 *)(row + 4 * u4) = h;
-        *(float4 *)(row + H + 4 * u4) = make_float4(cc[0], cc[32], cc[64], cc[96]);
-    }
-    const long ny = (long)a.B * k;                   // float4 units: ystage rows b < B are y's [B][k] prefix
-    for (long i = i0; i < ny; i += stride) ((float4 *)s.y)[i] = a.ystage[i];
-}
-
-// the same with +0.0 at frames t >= len[b] (ragged calls)
-__global__ void __launch_bounds__(256) seq_stream_writeback_ragged(const SeqStreamArgs s, const int32_t *len)
 {
     const StackArgs &a = s.a;
     const int k = a.T;
@@ -146,7 +118,7 @@ __global__ void __launch_bounds__(256) seq_stream_writeback_ragged(const SeqStre
     const long ny = (long)a.B * k;                   // float4 units: ystage rows b < B are y's [B][k] prefix
     for (long i = i0; i < ny; i += stride) {
         const float4 v = a.ystage[i];
-        ((float4 *)s.y)[i] = (int)(i % k) < stream_len(len, i / k, k) ? v : make_float4(0.f, 0.f, 0.f, 0.f);
+        ((float4 *)s.y)[i] = frame_kept(s.len, i, k, k) ? v : make_float4(0.f, 0.f, 0.f, 0.f);
     }
 }
 

@@ -40,7 +40,7 @@ from . import _lib
 from .datasets import FRAME_SHAPES, MAX_OBJECTS, _cone_table
 from .learned_models import BaselineLstm, NonLinearLstm, OPNet, OPNetLstmMlp, _stream_ptr
 from .object_indices import SNITCH_INDEX
-from .streaming import LstmStackStreams, OPNetStreams, check_lengths, upload_async
+from .streaming import LstmStackStreams, OPNetStreams, call_entry, upload_async
 
 TABLE_INTS = 16                # OPNET_ONLINE_TABLE_INTS: 15 class ids + the mode
 MODE_FIXED, MODE_LEARNED = 0, 1
@@ -231,21 +231,6 @@ class DetectorStreams:
         """a host array on the device without a host sync (streaming.upload_async)"""
         return upload_async(a, self.device)
 
-    def _ids_and_lengths(self, idx: np.ndarray, lengths, k: int):
-        """(slots, lengths) on the device without a host sync: host lengths are checked and go up with the slot ids in one
-        pinned copy; an int32 device tensor [n] is taken as is"""
-        n = idx.size
-        if lengths is None:
-            return self._upload(idx.astype(np.int32)), None
-        if isinstance(lengths, torch.Tensor) and lengths.is_cuda:
-            if lengths.device != self.device:
-                raise ValueError(f"lengths are on {lengths.device}, the streams on {self.device}")
-            if lengths.dtype != torch.int32 or tuple(lengths.shape) != (n,):
-                raise ValueError(f"device lengths must be int32 [n={n}], got {lengths.dtype} {tuple(lengths.shape)}")
-            return self._upload(idx.astype(np.int32)), lengths.contiguous()
-        both = self._upload(np.concatenate([idx.astype(np.int32), check_lengths(lengths, n, k)]))
-        return both[:n], both[n:]
-
     def _check_detections(self, ids, boxes, scores, labels, n_det):
         for t, name, dt in ((boxes, "boxes", torch.float32), (scores, "scores", torch.float32),
                             (labels, "labels", torch.int64), (n_det, "n_det", torch.int32)):
@@ -271,24 +256,18 @@ class DetectorStreams:
         n, k, md = int(boxes.shape[0]), int(boxes.shape[1]), int(boxes.shape[2])
         boxes, scores, labels, n_det = (t.contiguous() for t in (boxes, scores, labels, n_det))
         assert out.is_contiguous() and tuple(out.shape) == (n, k, MAX_OBJECTS, self.n_tracks)
-        lib = _lib.load()
-        if lengths is None:
-            rc = lib.opnet_online_encode_f32(
-                boxes.data_ptr(), scores.data_ptr(), labels.data_ptr(), n_det.data_ptr(), md, slots.data_ptr(),
-                self.tables.data_ptr(), self.capacity, self.cone_mask.data_ptr(), int(self.cone_mask.numel()), n, k,
-                self.n_tracks, self.score_thresh, out.data_ptr(), _stream_ptr(self.device))
-            _lib.check(rc, "opnet_online_encode_f32")
-        else:
-            rc = lib.opnet_online_encode_ragged_f32(
-                boxes.data_ptr(), scores.data_ptr(), labels.data_ptr(), n_det.data_ptr(), lengths.data_ptr(), md,
-                slots.data_ptr(), self.tables.data_ptr(), self.capacity, self.cone_mask.data_ptr(),
-                int(self.cone_mask.numel()), n, k, self.n_tracks, self.score_thresh, out.data_ptr(), _stream_ptr(self.device))
-            _lib.check(rc, "opnet_online_encode_ragged_f32")
+        call_entry("opnet_online_encode_f32",
+                   [boxes.data_ptr(), scores.data_ptr(), labels.data_ptr(), n_det.data_ptr(), md, slots.data_ptr(),
+                    self.tables.data_ptr(), self.capacity, self.cone_mask.data_ptr(), int(self.cone_mask.numel()), n, k,
+                    self.n_tracks, self.score_thresh, out.data_ptr(), _stream_ptr(self.device)], lengths, 4)
 
     def _encode(self, ids, boxes, scores, labels, n_det, lengths=None):
         idx, k, md = self._check_detections(ids, boxes, scores, labels, n_det)
         with torch.no_grad(), torch.cuda.device(self.device):
-            slots, lens = self._ids_and_lengths(idx, lengths, k)
+            if lengths is None:      # a pinned copy, unlike the pool's uniform route: encode never syncs the host
+                slots, lens = self._upload(idx.astype(np.int32)), None
+            else:
+                slots, lens = self.pool._device_ids(idx, lengths, k)
             x = torch.empty((idx.size, k, MAX_OBJECTS, self.n_tracks), dtype=torch.float32, device=self.device)
             self._encode_into(x, slots, boxes, scores, labels, n_det, lens)
         return slots, lens, x
@@ -384,7 +363,7 @@ class DetectorStreams:
         P = int(self.detector.MAX_FRAMES_PER_PASS)
         parts = []
         with torch.no_grad(), torch.cuda.device(self.device):
-            slots, lens = self._ids_and_lengths(idx, ks, K)
+            slots, lens = self.pool._device_ids(idx, ks, K)
             rows = self._upload(dest)
             for p0 in range(0, len(flat), P):
                 parts.append(self.detector._enqueue_padded(flat[p0:p0 + P], self.device))

@@ -108,9 +108,20 @@ def upload_async(a: np.ndarray, device) -> torch.Tensor:
     return torch.from_numpy(np.ascontiguousarray(a)).pin_memory().to(device, non_blocking=True)
 
 
+def call_entry(entry: str, args: list, lengths: Optional[torch.Tensor], at: int) -> None:
+    """the C entry `entry` (a `..._f32` of include/opnet_hip.h) on args, or for a ragged call (lengths given) its
+    `..._ragged_f32` twin, which takes the lengths pointer at position `at` of the same argument list"""
+    if lengths is not None:
+        entry = entry[:-len("_f32")] + "_ragged_f32"
+        args = args[:at] + [lengths.data_ptr()] + args[at:]
+    _lib.check(getattr(_lib.load(), entry)(*args), entry)
+
+
 class _StreamPool:
     """What every stream pool shares: the model's ROCm device, the slot bookkeeping, the state pool (one row of `row`
-    floats per slot, zero at open) and the per-(n, k, stream) workspaces."""
+    floats per slot, zero at open), the per-(n, k, stream) workspaces and the checks of `step`.  A subclass names its frame
+    argument (`_frames`, `_frames_are`: for error texts), sets its frame shape `_frame_shape` (S, F) and implements
+    `_step_slots`."""
 
     def __init__(self, model, capacity: int):
         slots = StreamSlots(capacity)
@@ -145,6 +156,25 @@ class _StreamPool:
     def close(self, ids: Sequence[int]) -> None:
         self.slots.close(ids)
 
+    # -- frames -------------------------------------------------------------------------------
+    def step(self, ids: Sequence[int], x: torch.Tensor, lengths=None):
+        """advance the streams `ids` by k frames: x [n, k, S, F] (row i belongs to ids[i]) -> the outputs of those frames
+        (OPNetStreams: boxes [n, k, 15, 6] -> (y [n, k, 4], logits [n, 15, k]); LstmStackStreams: x [n, k, 15, 5] ->
+        y [n, k, 4]).  lengths ([n] ints in 0..k, on the host or an int32 device tensor): stream i advances by its first
+        lengths[i] frames only; the outputs are +0.0 on the others."""
+        name = self._frames
+        if not isinstance(x, torch.Tensor) or not x.is_cuda:
+            raise RuntimeError(f"{type(self).__name__}.step runs on MI355X only: `{name}` must be a tensor on a ROCm device")
+        if x.device != self.device:
+            raise ValueError(f"{self._frames_are} on {x.device}, the stream pool on {self.device}")
+        idx = self.slots.check(ids)
+        n = idx.size
+        S, F = self._frame_shape
+        if x.dim() != 4 or x.shape[0] != n or x.shape[2] != S or x.shape[3] != F or x.shape[1] < 1:
+            raise ValueError(f"{name} must be [n={n}, k>=1, {S}, {F}], got {tuple(x.shape)}")
+        slots, lens = self._device_ids(idx, lengths, int(x.shape[1]))
+        return self._step_slots(slots, x, lens)
+
     def _device_ids(self, idx: np.ndarray, lengths, k: int):
         """(slots, lengths) on the device for a call of k frames: the uniform call (lengths None) uploads the slot ids as
         it always has; host lengths are checked and go up with the ids in one pinned copy; an int32 device tensor [n] is
@@ -167,6 +197,7 @@ class OPNetStreams(_StreamPool):
     """A pool of `capacity` OPNet (or OPNetLstmMlp) streams on the model's ROCm device.  Calls are enqueued on the
     current torch stream and are inference only (no autograd graph).  The model's own packed weight image is used, so an
     in-place parameter update takes effect on the next call."""
+    _frames, _frames_are, _frame_shape = "boxes", "boxes are", (15, 6)
 
     def __init__(self, model, capacity: int = 1024):
         if isinstance(model, OPNet):
@@ -223,24 +254,9 @@ class OPNetStreams(_StreamPool):
                 self.state.index_copy_(0, dst, torch.cat(cols, dim=1))
 
     # -- frames -------------------------------------------------------------------------------
-    def step(self, ids: Sequence[int], boxes: torch.Tensor, lengths=None):
-        """advance the streams `ids` by k frames: boxes [n, k, 15, 6] (row i belongs to ids[i]) -> (y [n, k, 4],
-        logits [n, 15, k]), the outputs of those frames.  lengths ([n] ints in 0..k, on the host or an int32 device
-        tensor): stream i advances by its first lengths[i] frames only; y / logits are +0.0 on the others."""
-        if not isinstance(boxes, torch.Tensor) or not boxes.is_cuda:
-            raise RuntimeError("OPNetStreams.step runs on MI355X only: `boxes` must be a tensor on a ROCm device")
-        if boxes.device != self.device:
-            raise ValueError(f"boxes are on {boxes.device}, the stream pool on {self.device}")
-        idx = self.slots.check(ids)
-        n = idx.size
-        if boxes.dim() != 4 or boxes.shape[0] != n or boxes.shape[2] != 15 or boxes.shape[3] != 6 or boxes.shape[1] < 1:
-            raise ValueError(f"boxes must be [n={n}, k>=1, 15, 6], got {tuple(boxes.shape)}")
-        slots, lens = self._device_ids(idx, lengths, int(boxes.shape[1]))
-        return self._step_slots(slots, boxes, lens)
-
     def _step_slots(self, slots: torch.Tensor, boxes: torch.Tensor, lengths: Optional[torch.Tensor] = None):
-        """step with the slot ids (and the lengths of a ragged call) already on the device (int32 [n], checked by the
-        caller) and boxes [n, k, 15, 6] checked: no host synchronisation"""
+        """boxes [n, k, 15, 6] -> (y [n, k, 4], logits [n, 15, k]), with the slot ids (and the lengths of a ragged call)
+        already on the device (int32 [n], checked by the caller) and boxes checked: no host synchronisation"""
         n, k = int(boxes.shape[0]), int(boxes.shape[1])
         lib = _lib.load()
         with torch.no_grad(), torch.cuda.device(self.device):
@@ -250,17 +266,10 @@ class OPNetStreams(_StreamPool):
             ws = self._ws.get(stream, (n, k), self.device, (lib.opnet_stream_workspace_bytes, n, k, self.H1, self.H2))
             y = torch.empty((n, k, 4), dtype=torch.float32, device=self.device)
             logits = torch.empty((n, 15, k), dtype=torch.float32, device=self.device)
-            if lengths is None:
-                rc = lib.opnet_stream_step_f32(boxes.data_ptr(), slots.data_ptr(), self.state.data_ptr(), packed.data_ptr(),
-                                               y.data_ptr(), logits.data_ptr(), ws.data_ptr(), ws.numel(), n, k,
-                                               self.capacity, self.H1, self.H2, self._mlp, stream)
-                _lib.check(rc, "opnet_stream_step_f32")
-            else:
-                rc = lib.opnet_stream_step_ragged_f32(boxes.data_ptr(), slots.data_ptr(), lengths.data_ptr(),
-                                                      self.state.data_ptr(), packed.data_ptr(), y.data_ptr(),
-                                                      logits.data_ptr(), ws.data_ptr(), ws.numel(), n, k, self.capacity,
-                                                      self.H1, self.H2, self._mlp, stream)
-                _lib.check(rc, "opnet_stream_step_ragged_f32")
+            call_entry("opnet_stream_step_f32",
+                            [boxes.data_ptr(), slots.data_ptr(), self.state.data_ptr(), packed.data_ptr(), y.data_ptr(),
+                             logits.data_ptr(), ws.data_ptr(), ws.numel(), n, k, self.capacity, self.H1, self.H2, self._mlp,
+                             stream], lengths, 2)
         return y, logits
 
 
@@ -269,6 +278,7 @@ class LstmStackStreams(_StreamPool):
     current torch stream and are inference only (no autograd graph).  The model's own packed weight image (the launch
     chain's, _LstmStackRunner._packed_weights) is used, so an in-place parameter update takes effect on the next call.
     A stream's state row is [h_0 | c_0 | h_1 | c_1 ...] over the model's L layers."""
+    _frames, _frames_are = "x", "x is"
 
     def __init__(self, model, capacity: int = 1024):
         if isinstance(model, NonLinearLstm):
@@ -283,6 +293,7 @@ class LstmStackStreams(_StreamPool):
         r = model._runner
         self.L, self.KX, self.H = r.L, r.KX, r.H
         self.slots_per_frame, self.features = model.max_objects_in_frame, model.bb_in_dim
+        self._frame_shape = (self.slots_per_frame, self.features)
         self._alloc_state(_lib.load().opseq_stream_state_floats(self.L, self.H), "opseq_stream_state_floats")
 
     # -- state --------------------------------------------------------------------------------
@@ -308,25 +319,9 @@ class LstmStackStreams(_StreamPool):
             self.state.index_copy_(0, torch.from_numpy(idx).to(self.device), rows)
 
     # -- frames -------------------------------------------------------------------------------
-    def step(self, ids: Sequence[int], x: torch.Tensor, lengths=None) -> torch.Tensor:
-        """advance the streams `ids` by k frames: x [n, k, 15, 5] (row i belongs to ids[i]) -> y [n, k, 4], the outputs
-        of those frames.  lengths ([n] ints in 0..k, on the host or an int32 device tensor): stream i advances by its
-        first lengths[i] frames only; y is +0.0 on the others."""
-        if not isinstance(x, torch.Tensor) or not x.is_cuda:
-            raise RuntimeError("LstmStackStreams.step runs on MI355X only: `x` must be a tensor on a ROCm device")
-        if x.device != self.device:
-            raise ValueError(f"x is on {x.device}, the stream pool on {self.device}")
-        idx = self.slots.check(ids)
-        n = idx.size
-        S, F = self.slots_per_frame, self.features
-        if x.dim() != 4 or x.shape[0] != n or x.shape[2] != S or x.shape[3] != F or x.shape[1] < 1:
-            raise ValueError(f"x must be [n={n}, k>=1, {S}, {F}], got {tuple(x.shape)}")
-        slots, lens = self._device_ids(idx, lengths, int(x.shape[1]))
-        return self._step_slots(slots, x, lens)
-
     def _step_slots(self, slots: torch.Tensor, x: torch.Tensor, lengths: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """step with the slot ids (and the lengths of a ragged call) already on the device (int32 [n], checked by the
-        caller) and x [n, k, 15, 5] checked: no host synchronisation"""
+        """x [n, k, 15, 5] -> y [n, k, 4], with the slot ids (and the lengths of a ragged call) already on the device
+        (int32 [n], checked by the caller) and x checked: no host synchronisation"""
         n, k = int(x.shape[0]), int(x.shape[1])
         S = self.slots_per_frame
         m = self.model
@@ -344,14 +339,7 @@ class LstmStackStreams(_StreamPool):
             packed = m._runner._packed_weights(m._runner.weights(m.video_LSTM, m.predictions_layer), self.device, stream)
             ws = self._ws.get(stream, (n, k), self.device, (lib.opseq_stream_workspace_bytes, n, k, self.L, self.KX, self.H))
             y = torch.empty((n, k, 4), dtype=torch.float32, device=self.device)
-            if lengths is None:
-                rc = lib.opseq_stream_step_f32(feats.data_ptr(), slots.data_ptr(), self.state.data_ptr(), packed.data_ptr(),
-                                               y.data_ptr(), ws.data_ptr(), ws.numel(), n, k, self.capacity, self.L, self.KX,
-                                               self.H, stream)
-                _lib.check(rc, "opseq_stream_step_f32")
-            else:
-                rc = lib.opseq_stream_step_ragged_f32(feats.data_ptr(), slots.data_ptr(), lengths.data_ptr(),
-                                                      self.state.data_ptr(), packed.data_ptr(), y.data_ptr(), ws.data_ptr(),
-                                                      ws.numel(), n, k, self.capacity, self.L, self.KX, self.H, stream)
-                _lib.check(rc, "opseq_stream_step_ragged_f32")
+            call_entry("opseq_stream_step_f32",
+                            [feats.data_ptr(), slots.data_ptr(), self.state.data_ptr(), packed.data_ptr(), y.data_ptr(),
+                             ws.data_ptr(), ws.numel(), n, k, self.capacity, self.L, self.KX, self.H, stream], lengths, 2)
         return y
