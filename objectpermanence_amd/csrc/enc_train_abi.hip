@@ -16,10 +16,7 @@ static void gemm_nt(const float *X, long XS, const float *Wt, long WS, const flo
         gemm_bias_act_ks<<<dim3((unsigned)((M + 31) / 32), (N + 31) / 32, 1), 256, 0, st>>>(X, Wt, bias, Y, (int)M, N, K, relu);
         return;
     }
-    ConvArgs c = {};
-    c.X = X; c.Wt = Wt; c.bias = bias; c.R = R; c.Y = Y;
-    c.N = 1; c.H = 1; c.W = (int)M; c.Cin = K; c.Cout = N; c.KH = 1; c.KW = 1; c.stride = 1; c.pad = 0;
-    c.OH = 1; c.OW = (int)M; c.KP = K; c.relu = relu;
+    ConvArgs c = row_gemm_args(X, Wt, bias, R, Y, M, N, K, relu);
     c.XS = (int)XS; c.WS = (int)WS; c.YS = (int)YS;
     const unsigned gx = (unsigned)((M + 127) / 128);
     // 128 x 128 tiles need well over one round of the chip's resident workgroups (3 a CU = 768) to even out: below ~1 300 of them the
@@ -68,16 +65,12 @@ static void gemm_nt_ks(const float *X, long XS, const float *Wt, long WS, float 
 {
     const int ks = (N & 3) ? 1 : gemm_split_slices(M, N, K);
     if (ks <= 1) { gemm_nt(X, XS, Wt, WS, nullptr, nullptr, Y, N, M, N, K, 0, st); return; }
-    ConvArgs c = {};
-    c.X = X; c.Wt = Wt; c.Y = Y;
-    c.N = 1; c.H = 1; c.W = (int)M; c.Cin = K; c.Cout = N; c.KH = 1; c.KW = 1; c.stride = 1; c.pad = 0;
-    c.OH = 1; c.OW = (int)M; c.KP = K;
+    ConvArgs c = row_gemm_args(X, Wt, nullptr, nullptr, Y, M, N, K, 0);
     c.XS = (int)XS; c.WS = (int)WS; c.YS = N;
     const int nhex = K >> 4, per = (nhex + ks - 1) / ks;
     c.P = part; c.ksteps = per; c.ksplit = (nhex + per - 1) / per;
     conv2d_nhwc_glds<64, 3><<<dim3((unsigned)((M + 127) / 128), (N + 63) / 64, c.ksplit), 256, 0, st>>>(c);
-    const long n4 = M * N / 4;
-    conv_splitk_reduce<<<(unsigned)((n4 + 255) / 256 > 4096 ? 4096 : (n4 + 255) / 256), 256, 0, st>>>(part, c.ksplit, M, N, nullptr, nullptr, Y, 0);
+    conv_splitk_reduce<<<ew_blocks(M * N / 4, 4096), 256, 0, st>>>(part, c.ksplit, M, N, nullptr, nullptr, Y, 0);
 }
 static const size_t kGemmSplitMax = 16;
 
@@ -96,16 +89,12 @@ static void gemm_nt_small(const float *X, long XS, const float *Wt, long WS, con
     int ks = (N & 3) || tiles >= 128 ? 1 : gemm_split_slices(M, N, K);
     while (ks > 1 && (size_t)ks * M * N > part_floats) --ks;
     if (ks <= 1) { gemm_nt(X, XS, Wt, WS, bias, R, Y, N, M, N, K, relu, st); return; }
-    ConvArgs c = {};
-    c.X = X; c.Wt = Wt; c.Y = Y;
-    c.N = 1; c.H = 1; c.W = (int)M; c.Cin = K; c.Cout = N; c.KH = 1; c.KW = 1; c.stride = 1; c.pad = 0;
-    c.OH = 1; c.OW = (int)M; c.KP = K;
+    ConvArgs c = row_gemm_args(X, Wt, nullptr, nullptr, Y, M, N, K, 0);
     c.XS = (int)XS; c.WS = (int)WS; c.YS = N;
     const int nhex = K >> 4, per = (nhex + ks - 1) / ks;
     c.P = part; c.ksteps = per; c.ksplit = (nhex + per - 1) / per;
     conv2d_nhwc_glds<64, 3><<<dim3((unsigned)((M + 127) / 128), (N + 63) / 64, c.ksplit), 256, 0, st>>>(c);
-    const long n4 = M * N / 4;
-    conv_splitk_reduce<<<(unsigned)((n4 + 255) / 256 > 4096 ? 4096 : (n4 + 255) / 256), 256, 0, st>>>(part, c.ksplit, M, N, bias, R, Y, relu);
+    conv_splitk_reduce<<<ew_blocks(M * N / 4, 4096), 256, 0, st>>>(part, c.ksplit, M, N, bias, R, Y, relu);
 }
 
 // ---- flash training attention (attn_train_kernels.hip) ---------------------------------------------------------------------

@@ -77,6 +77,17 @@ static bool conv_prefers_bn64(const ConvArgs &c, long M)
     return rounds128 > 1.0 && rounds128 < 1.4;
 }
 
+// the row GEMM  Y [M][N] = act(X [M][K] . Wt [N][K]^T + bias (+ R))  as the conv kernels take it: a 1 x 1 conv over M pixels
+static ConvArgs row_gemm_args(const float *X, const float *Wt, const float *bias, const float *R, float *Y, long M, int N, int K,
+                              int relu)
+{
+    ConvArgs c = {};
+    c.X = X; c.Wt = Wt; c.bias = bias; c.R = R; c.Y = Y;
+    c.N = 1; c.H = 1; c.W = (int)M; c.Cin = K; c.Cout = N; c.KH = 1; c.KW = 1; c.stride = 1; c.pad = 0;
+    c.OH = 1; c.OW = (int)M; c.KP = K; c.relu = relu;
+    return c;
+}
+
 // the LDS-staged conv / GEMM kernels: 128 x {128, 64} tiles; LDS-DMA staging (3 stages) needs Cin % 16 == 0
 static void launch_conv_tiled(const ConvArgs &c, long M, hipStream_t st)
 {
@@ -410,9 +421,7 @@ extern "C" size_t opnet_xcd_workspace_bytes(int B, int T, int H1, int H2)
 static unsigned long long *g_xcd_trace = nullptr;
 extern "C" void opnet_xcd_set_trace(void *device_buffer) { g_xcd_trace = (unsigned long long *)device_buffer; }
 
-// Two persistent launches must never be co-resident (each needs every CU of its XCDs: two half-resident grids would
-// wait for each other until the spin limit), so launches are chained per device through an event whatever streams
-// the callers use.
+// the chain of persistent launches per device (persistent_launch)
 static std::mutex g_xcd_mu;
 static hipEvent_t g_xcd_done[64] = {};
 // side streams of the sliced reverse recurrence (opnet_train_backward_f32), per device, created on first use
@@ -504,14 +513,93 @@ static int xcd_device_cus(int dev)
     return g_xcd_cus[dev];
 }
 
-// 1 when the persistent form can run on the CURRENT device for these sizes (reference hidden sizes, all 8 XCDs x 32 CUs
-// visible - not a compute partition), else 0: callers then use opnet_forward_f32 / opnet_plan_forward
+// a whole MI355X: all 8 XCDs x 32 CUs visible, not a compute partition - what every persistent kernel needs
+static bool whole_device(int dev) { return xcd_device_cus(dev) >= XCD_COUNT * XCD_CUS; }
+static bool whole_device()          // the current device
+{
+    int dev = 0;
+    return hipGetDevice(&dev) == hipSuccess && whole_device(dev);
+}
+
+// the current device for a persistent launch; refused (before the caller enqueues anything) unless it is whole
+static int persistent_device(int *dev)
+{
+    HIP_TRY(hipGetDevice(dev));
+    if (!whole_device(*dev))
+        return fail(OPNET_ESHAPE, "device %d exposes %d CUs; a persistent launch needs %d resident workgroups", *dev,
+                    xcd_device_cus(*dev), XCD_COUNT * XCD_CUS);
+    return OPNET_OK;
+}
+
+// Every persistent launch goes through here.  Two persistent launches must never be co-resident (each needs every CU of its
+// XCDs: two half-resident grids would wait for each other until the spin limit), so launches are chained per device through
+// one event whatever streams the callers use.  `launch()` enqueues the kernel on st; tag: its profile tag, -1 = none.
+template <class Launch>
+static int persistent_launch(int dev, hipStream_t st, int tag, Launch launch)
+{
+    if (dev < 0 || dev >= 64) return fail(OPNET_EINVAL, "device index %d out of range", dev);
+    std::lock_guard<std::mutex> lock(g_xcd_mu);
+    if (!g_xcd_done[dev]) HIP_TRY(hipEventCreateWithFlags(&g_xcd_done[dev], hipEventDisableTiming));
+    else HIP_TRY(hipStreamWaitEvent(st, g_xcd_done[dev], 0));
+    ProfPair pe{};
+    const bool prof = tag >= 0 && prof_begin(st, &pe);
+    launch();
+    if (prof) prof_end(tag, st, pe);
+    HIP_TRY(hipEventRecord(g_xcd_done[dev], st));
+    return OPNET_OK;
+}
+
+// 1 when the persistent form can run on the CURRENT device for these sizes (reference hidden sizes, a whole device), else 0:
+// callers then use opnet_forward_f32 / opnet_plan_forward
 extern "C" int opnet_xcd_supported(int H1, int H2)
 {
     if (H1 != XCD_H1 || H2 != XCD_H2) return 0;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return 0;
-    return xcd_device_cus(dev) >= XCD_COUNT * XCD_CUS ? 1 : 0;
+    return whole_device() ? 1 : 0;
+}
+
+// the arguments of opnet_xcd_forward over the workspace w, whose per-XCD layout L starts at byte `base` (0 for inference,
+// W.xcdws for training) and whose status words are at byte `status`
+static XcdArgs make_xcd_args(const XcdWorkspaceLayout &L, size_t base, size_t status, int B, int T, const float *packed, char *w,
+                             float *y, float *logits)
+{
+    XcdArgs a;
+    memset(&a, 0, sizeof(a));
+    a.B = B; a.T = T; a.NGT = L.NGT;
+    a.packed = packed;
+    a.xp = (const float4 *)(w + base + L.xp);
+    a.h1h = (float4 *)(w + base + L.h1h);
+    a.h2h = (float4 *)(w + base + L.h2h);
+    a.fbh = (float4 *)(w + base + L.fbh);
+    a.flags = (unsigned *)(w + base + L.flags);
+    a.status = (unsigned *)(w + status);
+    a.logits = logits;
+    a.ws = w;
+    a.xp_off = (unsigned)(base + L.xp); a.h1_off = (unsigned)(base + L.h1h); a.h2_off = (unsigned)(base + L.h2h);
+    a.fb_off = (unsigned)(base + L.fbh); a.flags_off = (unsigned)(base + L.flags); a.status_off = (unsigned)status;
+    a.ring = L.ring; a.yp_off = (unsigned)(base + L.yp); a.y = y;
+    a.force_safe = env_int("OPNET_XCD_SAFE", 0);
+    a.debug = env_int("OPNET_XCD_DEBUG", 0);
+    return a;
+}
+
+// opnet_xcd_forward<ho, TRAIN> between its input pack and its y epilogue
+template <bool TRAIN>
+static int xcd_forward_launch(const XcdSources &src, const XcdArgs &a, bool ho, int dev, hipStream_t st)
+{
+    opnet_xcd_pack_input<<<dim3(a.T + 2, a.NGT), 384, 0, st>>>(src, a);
+    if (int rc = persistent_launch(dev, st, PROF_XCD, [&] {
+            if (ho) opnet_xcd_forward<true, TRAIN><<<XCD_COUNT * XCD_CUS, 512, 0, st>>>(a);
+            else opnet_xcd_forward<false, TRAIN><<<XCD_COUNT * XCD_CUS, 512, 0, st>>>(a);
+        }))
+        return rc;
+    if (a.ring && ho)
+        opnet_xcd_y_poison<<<64, 256, 0, st>>>(a, a.y);      // y left the launch complete; NaN only if the launch gave up
+    else if (a.ring)
+        opnet_xcd_y_reduce<<<ew_blocks((long)a.NGT * a.T * 16, 2048), 256, 0, st>>>(a, a.y);
+    else
+        opnet_xcd_out_head<<<dim3(a.T, a.NGT), 256, 0, st>>>(a, a.y);
+    HIP_TRY(hipGetLastError());
+    return OPNET_OK;
 }
 
 static int xcd_forward_impl(const XcdSources &src, const float *packed, float *y, float *logits,
@@ -525,51 +613,10 @@ static int xcd_forward_impl(const XcdSources &src, const float *packed, float *y
     const XcdWorkspaceLayout L = xcd_workspace_layout(B, T);
     if (workspace_bytes < L.total) return fail(OPNET_EWORKSPACE, "workspace %zu B < %zu B", workspace_bytes, L.total);
     int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    if (dev < 0 || dev >= 64) return fail(OPNET_EINVAL, "device index %d out of range", dev);
-    hipStream_t st = (hipStream_t)stream;
-    char *w = (char *)workspace;
-    XcdArgs a;
-    a.B = B; a.T = T; a.NGT = L.NGT;
-    a.packed = packed;
-    a.xp = (const float4 *)(w + L.xp);
-    a.h1h = (float4 *)(w + L.h1h);
-    a.h2h = (float4 *)(w + L.h2h);
-    a.fbh = (float4 *)(w + L.fbh);
-    a.flags = (unsigned *)(w + L.flags);
-    a.status = (unsigned *)(w + L.status);
-    a.logits = logits;
-    a.ws = w;
-    a.xp_off = (unsigned)L.xp; a.h1_off = (unsigned)L.h1h; a.h2_off = (unsigned)L.h2h; a.fb_off = (unsigned)L.fbh; a.flags_off = (unsigned)L.flags; a.status_off = (unsigned)L.status;
-    a.ring = L.ring; a.yp_off = (unsigned)L.yp; a.y = y;
+    if (int rc = persistent_device(&dev)) return rc;
+    XcdArgs a = make_xcd_args(L, 0, L.status, B, T, packed, (char *)workspace, y, logits);
     a.trace = g_xcd_trace;
-    a.force_safe = env_int("OPNET_XCD_SAFE", 0);
-    a.debug = env_int("OPNET_XCD_DEBUG", 0);
-    const int cus = xcd_device_cus(dev);
-    if (cus < XCD_COUNT * XCD_CUS)
-        return fail(OPNET_ESHAPE, "device %d exposes %d CUs; the persistent forward needs %d resident workgroups", dev,
-                    cus, XCD_COUNT * XCD_CUS);
-    std::lock_guard<std::mutex> lock(g_xcd_mu);
-    opnet_xcd_pack_input<<<dim3(T + 2, L.NGT), 384, 0, st>>>(src, a);
-    if (!g_xcd_done[dev]) HIP_TRY(hipEventCreateWithFlags(&g_xcd_done[dev], hipEventDisableTiming));
-    else HIP_TRY(hipStreamWaitEvent(st, g_xcd_done[dev], 0));
-    ProfPair pe{};
-    const bool prof = prof_begin(st, &pe);
-    const int ho = L.ho;                    // xcd_head_once
-    if (ho) opnet_xcd_forward<true><<<XCD_COUNT * XCD_CUS, 512, 0, st>>>(a);
-    else opnet_xcd_forward<false><<<XCD_COUNT * XCD_CUS, 512, 0, st>>>(a);
-    if (prof) prof_end(PROF_XCD, st, pe);
-    HIP_TRY(hipEventRecord(g_xcd_done[dev], st));
-    if (a.ring && ho) {
-        opnet_xcd_y_poison<<<64, 256, 0, st>>>(a, y);      // y left the launch complete; NaN only if the launch gave up
-    } else if (a.ring) {
-        const long ny = (long)L.NGT * T * 16;
-        opnet_xcd_y_reduce<<<(unsigned)((ny + 255) / 256 > 2048 ? 2048 : (ny + 255) / 256), 256, 0, st>>>(a, y);
-    } else {
-        opnet_xcd_out_head<<<dim3(T, L.NGT), 256, 0, st>>>(a, y);
-    }
-    HIP_TRY(hipGetLastError());
-    return OPNET_OK;
+    return xcd_forward_launch<false>(src, a, L.ho, dev, (hipStream_t)stream);
 }
 
 extern "C" int opnet_xcd_forward_f32(const float *boxes, const float *packed, float *y, float *logits,
@@ -918,13 +965,6 @@ extern "C" void opnet_xcd4_enable(int on) { g_x4_enabled.store(on ? 1 : 0); }
 extern "C" int opnet_xcd4_enabled(void) { return g_x4_enabled.load(); }
 static bool x4_on() { return g_x4_enabled.load() != 0 && env_int("OPNET_XCD4", 1) != 0; }
 
-static bool x4_device()
-{
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return false;
-    return xcd_device_cus(dev) >= XCD_COUNT * XCD_CUS;
-}
-
 extern "C" int opnet_train_pack_weights_f32(const float *w_ih1, const float *w_hh1, const float *w_sel,
                                             const float *w_ih2, const float *w_hh2, const float *w_out,
                                             float *packed, size_t packed_bytes, int H1, int H2, void *stream)
@@ -936,7 +976,7 @@ extern "C" int opnet_train_pack_weights_f32(const float *w_ih1, const float *w_h
     if (packed_bytes < L.total * sizeof(float))
         return fail(OPNET_EWORKSPACE, "packed buffer %zu B < %zu B", packed_bytes, L.total * sizeof(float));
     hipStream_t st = (hipStream_t)stream;
-    bool lazy = x4_dims(H1, H2) && x4_on() && x4_device();
+    bool lazy = x4_dims(H1, H2) && x4_on() && whole_device();
     if (lazy) {
         std::lock_guard<std::mutex> lock(g_tp_mu);
         if (g_tp.find(packed) == g_tp.end() && g_tp.size() >= kTrainPackPending) lazy = false;      // no room to owe: pack in full
@@ -1125,10 +1165,7 @@ extern "C" int opnet_xcd4_forward_f32(const float *boxes, const float *packed, f
     const X4InferLayout L = x4_infer_layout(B, T);
     if (workspace_bytes < L.total) return fail(OPNET_EWORKSPACE, "workspace %zu B < %zu B", workspace_bytes, L.total);
     int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    if (xcd_device_cus(dev) < XCD_COUNT * XCD_CUS)
-        return fail(OPNET_ESHAPE, "device %d exposes %d CUs; the persistent forward needs %d resident workgroups", dev,
-                    xcd_device_cus(dev), XCD_COUNT * XCD_CUS);
+    if (int rc = persistent_device(&dev)) return rc;
     hipStream_t st = (hipStream_t)stream;
     char *w = (char *)workspace;
     const X4InferPacked PK = x4_infer_packed_layout();
@@ -1161,11 +1198,8 @@ extern "C" int opnet_xcd4_forward_f32(const float *boxes, const float *packed, f
     opnet_set_io<<<1, 1, 0, st>>>(dio, io);
     opnet_pack_input<<<dim3(T, RB), 256, 0, st>>>(dio);
     opnet_xcd4_init<<<8, 256, 0, st>>>(x);
-    std::lock_guard<std::mutex> lock(g_xcd_mu);
-    if (!g_xcd_done[dev]) HIP_TRY(hipEventCreateWithFlags(&g_xcd_done[dev], hipEventDisableTiming));
-    else HIP_TRY(hipStreamWaitEvent(st, g_xcd_done[dev], 0));
-    opnet_xcd4_forward<false><<<XCD_COUNT * XCD_CUS, 256, 0, st>>>(x);
-    HIP_TRY(hipEventRecord(g_xcd_done[dev], st));
+    if (int rc = persistent_launch(dev, st, -1, [&] { opnet_xcd4_forward<false><<<XCD_COUNT * XCD_CUS, 256, 0, st>>>(x); }))
+        return rc;
     opnet_xcd4_out_head<<<dim3(T, RB), 256, 0, st>>>(x, nullptr, nullptr);
     opnet_copy_out<<<copy_grid(B, T), 256, 0, st>>>(dio);
     HIP_TRY(hipGetLastError());
@@ -1185,9 +1219,7 @@ static bool x4_use(int B, int T, int H1, int H2, bool forward = false)
     const int cap = getenv("OPNET_XCD4_MAX_B") ? env_int("OPNET_XCD4_MAX_B", 32) : (forward ? env_int("OPNET_XCD4_FWD_MAX_B", 96) : 32);
     if (B > cap) return false;
     if (train_workspace_layout(B, T, H1, H2).total >= ((size_t)1 << 31)) return false;   // one buffer descriptor
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return false;
-    return xcd_device_cus(dev) >= XCD_COUNT * XCD_CUS;
+    return whole_device();
 }
 
 // Does the training forward of this batch run as the 16-clip persistent launch?  (OPNET_XCD_TRAIN=0 keeps the chain; the switch of
@@ -1197,9 +1229,7 @@ static bool xcdt_use(int B, int T, int H1, int H2)
     if (!xcdt_batch(B, H1, H2) || !x4_on() || env_int("OPNET_XCD_TRAIN", 1) == 0) return false;
     if (B < env_int("OPNET_XCD_TRAIN_MIN_B", 97)) return false;
     if (train_workspace_layout(B, T, H1, H2).total >= ((size_t)1 << 31)) return false;   // one buffer descriptor, 32-bit offsets
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return false;
-    return xcd_device_cus(dev) >= XCD_COUNT * XCD_CUS;
+    return whole_device();
 }
 
 static int make_x4_args(Xcd4Args *x, const float *packed, void *ws, int B, int T, int H1, int H2)
@@ -1265,15 +1295,12 @@ extern "C" int opnet_train_forward_f32(const float *boxes, const float *packed, 
         Xcd4Args x;
         if (int rc = make_x4_args(&x, packed, workspace, B, T, H1, H2)) return rc;
         int dev = 0;
-        HIP_TRY(hipGetDevice(&dev));
+        if (int rc = persistent_device(&dev)) return rc;
         OpnetIO io_nz = io;
         io_nz.state_f4 = 0;                     // (the prologue zeroes slot 0 of the histories itself)
         opnet_x4_train_prologue<<<dim3(T, a.RB + 1), 256, 0, st>>>(dio, io_nz, x);
-        std::lock_guard<std::mutex> lock(g_xcd_mu);
-        if (!g_xcd_done[dev]) HIP_TRY(hipEventCreateWithFlags(&g_xcd_done[dev], hipEventDisableTiming));
-        else HIP_TRY(hipStreamWaitEvent(st, g_xcd_done[dev], 0));
-        opnet_xcd4_forward<true><<<XCD_COUNT * XCD_CUS, 256, 0, st>>>(x);
-        HIP_TRY(hipEventRecord(g_xcd_done[dev], st));
+        if (int rc = persistent_launch(dev, st, -1, [&] { opnet_xcd4_forward<true><<<XCD_COUNT * XCD_CUS, 256, 0, st>>>(x); }))
+            return rc;
         opnet_xcd4_out_head<<<dim3(T, a.RB + 1), 256, 0, st>>>(x, (float4 *)y, logits);
         HIP_TRY(hipGetLastError());
         return OPNET_OK;
@@ -1287,26 +1314,9 @@ extern "C" int opnet_train_forward_f32(const float *boxes, const float *packed, 
         const XcdWorkspaceLayout L = xcd_workspace_layout(B, T);
         char *w = (char *)workspace;
         int dev = 0;
-        HIP_TRY(hipGetDevice(&dev));
-        XcdArgs xa;
-        memset(&xa, 0, sizeof(xa));
-        xa.B = B; xa.T = T; xa.NGT = L.NGT;
-        xa.packed = packed;                     // (the inference image comes first in the training image)
-        xa.xp = (const float4 *)(w + W.xcdws + L.xp);
-        xa.h1h = (float4 *)(w + W.xcdws + L.h1h);
-        xa.h2h = (float4 *)(w + W.xcdws + L.h2h);
-        xa.fbh = (float4 *)(w + W.xcdws + L.fbh);
-        xa.flags = (unsigned *)(w + W.xcdws + L.flags);
-        xa.status = (unsigned *)(w + train_status_offset(W, B, T, H1, H2));
-        xa.logits = logits;
-        xa.ws = w;
-        xa.xp_off = (unsigned)(W.xcdws + L.xp); xa.h1_off = (unsigned)(W.xcdws + L.h1h); xa.h2_off = (unsigned)(W.xcdws + L.h2h);
-        xa.fb_off = (unsigned)(W.xcdws + L.fbh); xa.flags_off = (unsigned)(W.xcdws + L.flags);
-        xa.status_off = (unsigned)train_status_offset(W, B, T, H1, H2);
-        xa.ring = L.ring; xa.yp_off = (unsigned)(W.xcdws + L.yp); xa.y = y;
-        xa.trace = nullptr;
-        xa.force_safe = env_int("OPNET_XCD_SAFE", 0);
-        xa.debug = env_int("OPNET_XCD_DEBUG", 0);
+        if (int rc = persistent_device(&dev)) return rc;
+        // (the inference image comes first in the training image)
+        XcdArgs xa = make_xcd_args(L, W.xcdws, train_status_offset(W, B, T, H1, H2), B, T, packed, w, y, logits);
         xa.tr_h1 = (unsigned)W.h1all; xa.tr_c1 = (unsigned)W.c1all; xa.tr_h2 = (unsigned)W.h2all; xa.tr_c2 = (unsigned)W.c2all;
         xa.tr_g1 = (unsigned)W.g1; xa.tr_g2 = (unsigned)W.g2; xa.tr_ps = (unsigned)W.psave; xa.tr_x2 = (unsigned)W.x2all;
         xa.RB = a.RB;
@@ -1321,26 +1331,7 @@ extern "C" int opnet_train_forward_f32(const float *boxes, const float *packed, 
             HIP_TRY(hipMemsetAsync(w + W.psave, 0, (size_t)T * a.RB * 128 * 16, st));
             HIP_TRY(hipMemsetAsync(w + W.x2all, 0, (size_t)T * a.RB * 64 * 16, st));
         }
-        std::lock_guard<std::mutex> lock(g_xcd_mu);
-        opnet_xcd_pack_input<<<dim3(T + 2, L.NGT), 384, 0, st>>>(src, xa);
-        if (!g_xcd_done[dev]) HIP_TRY(hipEventCreateWithFlags(&g_xcd_done[dev], hipEventDisableTiming));
-        else HIP_TRY(hipStreamWaitEvent(st, g_xcd_done[dev], 0));
-        ProfPair pe{};
-        const bool prof = prof_begin(st, &pe);
-        if (L.ho) opnet_xcd_forward<true, true><<<XCD_COUNT * XCD_CUS, 512, 0, st>>>(xa);
-        else opnet_xcd_forward<false, true><<<XCD_COUNT * XCD_CUS, 512, 0, st>>>(xa);
-        if (prof) prof_end(PROF_XCD, st, pe);
-        HIP_TRY(hipEventRecord(g_xcd_done[dev], st));
-        if (xa.ring && L.ho) {
-            opnet_xcd_y_poison<<<64, 256, 0, st>>>(xa, y);
-        } else if (xa.ring) {
-            const long ny = (long)L.NGT * T * 16;
-            opnet_xcd_y_reduce<<<(unsigned)((ny + 255) / 256 > 2048 ? 2048 : (ny + 255) / 256), 256, 0, st>>>(xa, y);
-        } else {
-            opnet_xcd_out_head<<<dim3(T, L.NGT), 256, 0, st>>>(xa, y);
-        }
-        HIP_TRY(hipGetLastError());
-        return OPNET_OK;
+        return xcd_forward_launch<true>(src, xa, L.ho, dev, st);
     }
     // the status words of the persistent kernels are sticky from the forward to the weight-gradient launch and the optimiser's
     // guard: a forward on the launch chain has to say "nothing aborted" itself
@@ -1493,14 +1484,11 @@ static int train_backward_impl(const float *dy, const float *packed, void *works
         Xcd4BArgs x;
         make_x4b_args(&x, packed, workspace, B, T, H1, H2);
         int dev = 0;
-        HIP_TRY(hipGetDevice(&dev));
+        if (int rc = persistent_device(&dev)) return rc;
         opnet_xcd4_init_bwd<<<256, 256, 0, st>>>(x, (const float4 *)dy, (float4 *)(w + W.dyp), (float *)(w + W.dcz),
                                                  (long)((W.dcz_end - W.dcz) / 4), B);
-        std::lock_guard<std::mutex> lock(g_xcd_mu);
-        if (!g_xcd_done[dev]) HIP_TRY(hipEventCreateWithFlags(&g_xcd_done[dev], hipEventDisableTiming));
-        else HIP_TRY(hipStreamWaitEvent(st, g_xcd_done[dev], 0));
-        opnet_xcd4_backward<<<XCD_COUNT * XCD_CUS, 256, 0, st>>>(x);
-        HIP_TRY(hipEventRecord(g_xcd_done[dev], st));
+        if (int rc = persistent_launch(dev, st, -1, [&] { opnet_xcd4_backward<<<XCD_COUNT * XCD_CUS, 256, 0, st>>>(x); }))
+            return rc;
     } else if (int rc = mlp ? OPNET_OK : train_chain_layouts(packed, st)) {      // (the mlp image is always packed eagerly)
         return rc;
     } else if (sliced) {
@@ -1926,22 +1914,17 @@ static dim3 stack_args_inference(StackArgs *ap, char *w, const float *packed, in
     return dim3((ntiles + 7) / 8 * 8, RB < OPNET_MAX_GY ? RB : OPNET_MAX_GY, 1);   // XCD-aligned, see step_grid
 }
 
-// the hoisted layer-0 input product through the tiled GEMM: G [B*T][4H] = x [B*T][KX] . W_ih0^T (a 1x1 "conv" over B*T
-// pixels, into the workspace w), then into the step kernel's layout xg [T][RB][H][32]
+// the hoisted layer-0 input product through the tiled GEMM: G [B*T][4H] = x [B*T][KX] . W_ih0^T (into the workspace w), then
+// into the step kernel's layout xg [T][RB][H][32]
 static void stack_hoisted_input_tiled(const float *x, const float *packed, char *w, float4 *xg, int B, int T, int L, int KX,
                                       int H, hipStream_t st)
 {
     const StackWorkspaceLayout W = stack_workspace_layout(B, T, L, KX, H);
     const StackPackedLayout P = stack_packed_layout(L, KX, H);
     const int RB = (B + 31) / 32;
-    ConvArgs c = {};
-    c.X = x; c.Wt = packed + P.wih0g; c.bias = nullptr; c.R = nullptr; c.Y = (float *)(w + W.gemm);
-    c.N = 1; c.H = 1; c.W = B * T; c.Cin = KX; c.Cout = 4 * H; c.KH = 1; c.KW = 1; c.stride = 1; c.pad = 0;
-    c.OH = 1; c.OW = B * T; c.KP = KX; c.relu = 0;
-    launch_conv_tiled(c, (long)B * T, st);
-    const long nx = (long)T * RB * 32 * H;
-    stack_xg_repack<<<(unsigned)((nx + 255) / 256 > 8192 ? 8192 : (nx + 255) / 256), 256, 0, st>>>(
-        (const float4 *)(w + W.gemm), xg, B, T, RB, H);
+    launch_conv_tiled(row_gemm_args(x, packed + P.wih0g, nullptr, nullptr, (float *)(w + W.gemm), (long)B * T, 4 * H, KX, 0),
+                      (long)B * T, st);
+    stack_xg_repack<<<ew_blocks((long)T * RB * 32 * H, 8192), 256, 0, st>>>((const float4 *)(w + W.gemm), xg, B, T, RB, H);
 }
 
 static int stack_forward_impl(const float *x, const float *packed, float *y, void *workspace,
@@ -2033,7 +2016,7 @@ extern "C" void opseq_xcd_enable(int on) { g_seqx_enabled.store(on ? 1 : 0); }
 extern "C" int opseq_xcd_supported(int L, int KX, int H)
 {
     if (!seqx_dims(L, KX, H) || g_seqx_enabled.load() == 0 || env_int("OPSEQ_XCD", 1) == 0) return 0;
-    return x4_device() ? 1 : 0;
+    return whole_device() ? 1 : 0;
 }
 extern "C" int opseq_xcd_max_batch(int L) { return L == 2 ? 4 * SX_NGMAX * 4 : 4 * SX_NGMAX * 8; }
 
@@ -2110,6 +2093,17 @@ extern "C" int opseq_xcd_pack_weights_f32(const float *const *w_ih, const float 
     return OPNET_OK;
 }
 
+// seqx_forward<KXQ, L, TRAIN> through the gate (KXQ: k-quads of layer 0's direct input, 0 = hoisted)
+template <bool TRAIN>
+static int seqx_forward_launch(const SeqXArgs &a, int dev, hipStream_t st)
+{
+    return persistent_launch(dev, st, PROF_SEQX, [&] {
+        if (a.L == 1) seqx_forward<20, 1, TRAIN><<<XCD_COUNT * XCD_CUS, 256, 0, st>>>(a);
+        else if (a.KXQ == 64) seqx_forward<64, 2, TRAIN><<<XCD_COUNT * XCD_CUS, 256, 0, st>>>(a);
+        else seqx_forward<0, 2, TRAIN><<<XCD_COUNT * XCD_CUS, 256, 0, st>>>(a);
+    });
+}
+
 /* y [B][T][4] = head(LSTM stack(x [B][T][KX])) as ONE persistent launch (+ input pack / hoisted GEMM before, the 4-row head
  * after).  packed: opseq_xcd_pack_weights_f32 image; w_head: predictions_layer.weight [4][H] as the caller holds it. */
 extern "C" int opseq_xcd_forward_f32(const float *x, const float *packed, const float *w_head, float *y, void *workspace,
@@ -2122,10 +2116,7 @@ extern "C" int opseq_xcd_forward_f32(const float *x, const float *packed, const 
     const SeqXWs W = seqx_ws_layout(B, T, L, KX, H);
     if (workspace_bytes < W.total) return fail(OPNET_EWORKSPACE, "workspace %zu B < %zu B", workspace_bytes, W.total);
     int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    if (xcd_device_cus(dev) < XCD_COUNT * XCD_CUS)
-        return fail(OPNET_ESHAPE, "device %d exposes %d CUs; the persistent launch needs %d resident workgroups", dev,
-                    xcd_device_cus(dev), XCD_COUNT * XCD_CUS);
+    if (int rc = persistent_device(&dev)) return rc;
     const SeqXHostPacked PK = seqx_host_packed(L, KX, H);
     const int nxq0 = seqx_nxq0(KX, H);
     hipStream_t st = (hipStream_t)stream;
@@ -2146,28 +2137,14 @@ extern "C" int opseq_xcd_forward_f32(const float *x, const float *packed, const 
     a.trace = g_seqx_trace;
     if (nxq0 == 0) {
         if (!aligned16(x)) return fail(OPNET_EINVAL, "x must be 16-byte aligned");
-        // G [B*T][4H] = x [B*T][KX] . W_ih0^T (a 1 x 1 "conv" over B*T pixels); the cell reads it where it lies
-        ConvArgs c = {};
-        c.X = x; c.Wt = packed + PK.wih0g; c.bias = nullptr; c.R = nullptr; c.Y = (float *)(w + W.gemm);
-        c.N = 1; c.H = 1; c.W = B * T; c.Cin = KX; c.Cout = 4 * H; c.KH = 1; c.KW = 1; c.stride = 1; c.pad = 0;
-        c.OH = 1; c.OW = B * T; c.KP = KX; c.relu = 0;
-        launch_conv_tiled(c, (long)B * T, st);
+        // G [B*T][4H] = x [B*T][KX] . W_ih0^T; the cell reads it where it lies
+        launch_conv_tiled(row_gemm_args(x, packed + PK.wih0g, nullptr, nullptr, (float *)(w + W.gemm), (long)B * T, 4 * H, KX, 0),
+                          (long)B * T, st);
     } else {
         rows_to_packed<<<1024, 256, 0, st>>>(x, (float4 *)(w + W.xp), B, T, RB, KX, 4 * nxq0, nullptr, 0);
     }
     seqx_init<<<512, 256, 0, st>>>(a);
-    {
-        std::lock_guard<std::mutex> lock(g_xcd_mu);           // two persistent grids must never be co-resident
-        if (!g_xcd_done[dev]) HIP_TRY(hipEventCreateWithFlags(&g_xcd_done[dev], hipEventDisableTiming));
-        else HIP_TRY(hipStreamWaitEvent(st, g_xcd_done[dev], 0));
-        ProfPair pe{};
-        const bool prof = prof_begin(st, &pe);
-        if (L == 1) seqx_forward<20, 1, false><<<XCD_COUNT * XCD_CUS, 256, 0, st>>>(a);
-        else if (nxq0 == 64) seqx_forward<64, 2, false><<<XCD_COUNT * XCD_CUS, 256, 0, st>>>(a);
-        else seqx_forward<0, 2, false><<<XCD_COUNT * XCD_CUS, 256, 0, st>>>(a);
-        if (prof) prof_end(PROF_SEQX, st, pe);
-        HIP_TRY(hipEventRecord(g_xcd_done[dev], st));
-    }
+    if (int rc = seqx_forward_launch<false>(a, dev, st)) return rc;
     seqx_out_head<<<dim3(T, a.NGT), 64, 0, st>>>(a);
     HIP_TRY(hipGetLastError());
     return OPNET_OK;
@@ -2193,7 +2170,7 @@ extern "C" void opseq_xcdt_enable(int on) { g_seqt_enabled.store(on ? 1 : 0); }
 extern "C" int opseq_xcdt_supported(int L, int KX, int H)
 {
     if (!seqt_mode(L, KX, H) || g_seqt_enabled.load() == 0 || env_int("OPSEQ_XCDT", 1) == 0) return 0;
-    return x4_device() ? 1 : 0;
+    return whole_device() ? 1 : 0;
 }
 struct SeqTHostPacked { size_t regs, wih0g, total; };          // floats
 static SeqTHostPacked seqt_host_packed(int mode, int KX)
@@ -2298,10 +2275,7 @@ extern "C" int opseq_xcdt_forward_f32(const float *x, const float *packed, const
     const SeqTWs W = seqt_ws_layout(B, T, mode, KX);
     if (workspace_bytes < W.total) return fail(OPNET_EWORKSPACE, "workspace %zu B < %zu B", workspace_bytes, W.total);
     int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    if (xcd_device_cus(dev) < XCD_COUNT * XCD_CUS)
-        return fail(OPNET_ESHAPE, "device %d exposes %d CUs; the persistent launch needs %d resident workgroups", dev,
-                    xcd_device_cus(dev), XCD_COUNT * XCD_CUS);
+    if (int rc = persistent_device(&dev)) return rc;
     const SeqTHostPacked PK = seqt_host_packed(mode, KX);
     hipStream_t st = (hipStream_t)stream;
     char *w = (char *)workspace;
@@ -2322,25 +2296,16 @@ extern "C" int opseq_xcdt_forward_f32(const float *x, const float *packed, const
     a.trace = g_seqt_trace;
     if (mode == 2) {
         if (!aligned16(x)) return fail(OPNET_EINVAL, "x must be 16-byte aligned");
-        // G [B*T][4H] = x [B*T][KX] . W_ih0^T (a 1 x 1 "conv" over B*T pixels); the layer-0 cell reads it where it lies
-        ConvArgs c = {};
-        c.X = x; c.Wt = packed + PK.wih0g; c.bias = nullptr; c.R = nullptr; c.Y = (float *)(w + W.g);
-        c.N = 1; c.H = 1; c.W = B * T; c.Cin = KX; c.Cout = 4 * H; c.KH = 1; c.KW = 1; c.stride = 1; c.pad = 0;
-        c.OH = 1; c.OW = B * T; c.KP = KX; c.relu = 0;
+        // G [B*T][4H] = x [B*T][KX] . W_ih0^T; the layer-0 cell reads it where it lies
+        const ConvArgs c = row_gemm_args(x, packed + PK.wih0g, nullptr, nullptr, (float *)(w + W.g), (long)B * T, 4 * H, KX, 0);
         if (int rc = launch_gemm_k256(c, (long)B * T, st)) return rc;
     }
     seqt_init<<<1024, 256, 0, st>>>(a, x);
-    {
-        std::lock_guard<std::mutex> lock(g_xcd_mu);           // two persistent grids must never be co-resident
-        if (!g_xcd_done[dev]) HIP_TRY(hipEventCreateWithFlags(&g_xcd_done[dev], hipEventDisableTiming));
-        else HIP_TRY(hipStreamWaitEvent(st, g_xcd_done[dev], 0));
-        ProfPair pe{};
-        const bool prof = prof_begin(st, &pe);
-        if (mode == 1) seqt_forward<1><<<XCD_COUNT * XCD_CUS, 512, 0, st>>>(a);
-        else seqt_forward<2><<<XCD_COUNT * XCD_CUS, 512, 0, st>>>(a);
-        if (prof) prof_end(PROF_SEQT, st, pe);
-        HIP_TRY(hipEventRecord(g_xcd_done[dev], st));
-    }
+    if (int rc = persistent_launch(dev, st, PROF_SEQT, [&] {
+            if (mode == 1) seqt_forward<1><<<XCD_COUNT * XCD_CUS, 512, 0, st>>>(a);
+            else seqt_forward<2><<<XCD_COUNT * XCD_CUS, 512, 0, st>>>(a);
+        }))
+        return rc;
     seqt_out_head<<<dim3(T, a.NGT), 256, 0, st>>>(a);
     HIP_TRY(hipGetLastError());
     return OPNET_OK;
@@ -2563,14 +2528,10 @@ extern "C" int opseq_lstm_stack_train_forward_f32(const float *x, const float *p
         // by the weight-gradient GEMM.  Scratch: G lives in the da-rows buffer (used by backward only), xg in layer
         // 0's gate-save buffer - every thread reads its xg element before it overwrites it with the saved gates.
         if (!aligned16(x)) return fail(OPNET_EINVAL, "x must be 16-byte aligned");
-        ConvArgs c = {};
-        c.X = x; c.Wt = packed + P.wih0g; c.bias = nullptr; c.R = nullptr; c.Y = (float *)(w + W.darows);
-        c.N = 1; c.H = 1; c.W = B * T; c.Cin = KX; c.Cout = 4 * H; c.KH = 1; c.KW = 1; c.stride = 1; c.pad = 0;
-        c.OH = 1; c.OW = B * T; c.KP = KX; c.relu = 0;
-        launch_conv_tiled(c, (long)B * T, st);
-        const long nx = (long)T * a.RB * 32 * H;
+        launch_conv_tiled(row_gemm_args(x, packed + P.wih0g, nullptr, nullptr, (float *)(w + W.darows), (long)B * T, 4 * H, KX, 0),
+                          (long)B * T, st);
         if (!use_sx)
-            stack_xg_repack<<<(unsigned)((nx + 255) / 256 > 8192 ? 8192 : (nx + 255) / 256), 256, 0, st>>>(
+            stack_xg_repack<<<ew_blocks((long)T * a.RB * 32 * H, 8192), 256, 0, st>>>(
                 (const float4 *)(w + W.darows), (float4 *)(w + W.g[0]), B, T, a.RB, H);
         a.layer[0].xg = (float4 *)(w + W.g[0]);
         a.layer[0].a_skip = P.nhx[0];
@@ -2581,12 +2542,11 @@ extern "C" int opseq_lstm_stack_train_forward_f32(const float *x, const float *p
         // inference forward of this shape (bit-identical y) + the h / c / gate histories the backward below reads, written in
         // the launch chain's own layouts.  (The hoisted input product: the cell reads G where the GEMM left it - W.darows.)
         const StackTrainPacked TP = stack_train_packed_layout(L, KX, H);
-        const int nxq0 = seqx_nxq0(KX, H);
         int dev = 0;
-        HIP_TRY(hipGetDevice(&dev));
+        if (int rc = persistent_device(&dev)) return rc;
         SeqXArgs sx;
         memset(&sx, 0, sizeof(sx));
-        sx.B = B; sx.T = T; sx.L = L; sx.NGT = (B + 3) / 4; sx.RB = a.RB; sx.KXQ = nxq0;
+        sx.B = B; sx.T = T; sx.L = L; sx.NGT = (B + 3) / 4; sx.RB = a.RB; sx.KXQ = seqx_nxq0(KX, H);
         sx.pk = packed + TP.seqx;
         sx.whead = packed + TP.whead;
         sx.ws = w;
@@ -2609,18 +2569,7 @@ extern "C" int opseq_lstm_stack_train_forward_f32(const float *x, const float *p
         if (sx.NGT * 4 < a.RB * 32)
             for (int l = 0; l < L; ++l)
                 HIP_TRY(hipMemsetAsync(w + W.g[l], 0, (size_t)T * a.RB * (size_t)H * 32 * 16, st));
-        {
-            std::lock_guard<std::mutex> lock(g_xcd_mu);
-            if (!g_xcd_done[dev]) HIP_TRY(hipEventCreateWithFlags(&g_xcd_done[dev], hipEventDisableTiming));
-            else HIP_TRY(hipStreamWaitEvent(st, g_xcd_done[dev], 0));
-            ProfPair pe{};
-            const bool prof = prof_begin(st, &pe);
-            if (L == 1) seqx_forward<20, 1, true><<<XCD_COUNT * XCD_CUS, 256, 0, st>>>(sx);
-            else if (nxq0 == 64) seqx_forward<64, 2, true><<<XCD_COUNT * XCD_CUS, 256, 0, st>>>(sx);
-            else seqx_forward<0, 2, true><<<XCD_COUNT * XCD_CUS, 256, 0, st>>>(sx);
-            if (prof) prof_end(PROF_SEQX, st, pe);
-            HIP_TRY(hipEventRecord(g_xcd_done[dev], st));
-        }
+        if (int rc = seqx_forward_launch<true>(sx, dev, st)) return rc;
         seqx_out_head<<<dim3(T, sx.NGT), 64, 0, st>>>(sx);
         HIP_TRY(hipGetLastError());
         return OPNET_OK;
@@ -2631,7 +2580,7 @@ extern "C" int opseq_lstm_stack_train_forward_f32(const float *x, const float *p
     const stack_step_fn stepk = stack_step_kernel(a.RB);
     for (int s = 0; s < T + 2 * L - 1; ++s) stepk<<<grid, stack_step_threads(a.RB), 0, st>>>(a, s);
     const long ny = (long)B * T;
-    copy_y_out<<<(unsigned)((ny + 255) / 256 > 1024 ? 1024 : (ny + 255) / 256), 256, 0, st>>>(a.ystage, (float4 *)y, ny);
+    copy_y_out<<<ew_blocks(ny, 1024), 256, 0, st>>>(a.ystage, (float4 *)y, ny);
     HIP_TRY(hipGetLastError());
     return OPNET_OK;
 }
@@ -2662,7 +2611,7 @@ extern "C" int opseq_lstm_stack_train_backward_f32(const float *dy, const float 
     unsigned *sxb_status = nullptr;
     if (use_sxb) {
         int dev = 0;
-        HIP_TRY(hipGetDevice(&dev));
+        if (int rc = persistent_device(&dev)) return rc;
         SeqXBArgs sb;
         memset(&sb, 0, sizeof(sb));
         sb.B = B; sb.T = T; sb.L = L; sb.NGT = (B + 3) / 4; sb.RB = RB;
@@ -2677,17 +2626,11 @@ extern "C" int opseq_lstm_stack_train_backward_f32(const float *dy, const float 
         sb.force_safe = env_int("OPNET_XCD_SAFE", 0);
         sb.debug = env_int("OPSEQ_XCD_DEBUG", 0);
         seqxb_init<<<512, 256, 0, st>>>(sb);
-        {
-            std::lock_guard<std::mutex> lock(g_xcd_mu);
-            if (!g_xcd_done[dev]) HIP_TRY(hipEventCreateWithFlags(&g_xcd_done[dev], hipEventDisableTiming));
-            else HIP_TRY(hipStreamWaitEvent(st, g_xcd_done[dev], 0));
-            ProfPair pe{};
-            const bool prof = prof_begin(st, &pe);
-            if (L == 1) seqx_backward<1><<<XCD_COUNT * XCD_CUS, 256, 0, st>>>(sb);
-            else seqx_backward<2><<<XCD_COUNT * XCD_CUS, 256, 0, st>>>(sb);
-            if (prof) prof_end(PROF_SEQXB, st, pe);
-            HIP_TRY(hipEventRecord(g_xcd_done[dev], st));
-        }
+        if (int rc = persistent_launch(dev, st, PROF_SEQXB, [&] {
+                if (L == 1) seqx_backward<1><<<XCD_COUNT * XCD_CUS, 256, 0, st>>>(sb);
+                else seqx_backward<2><<<XCD_COUNT * XCD_CUS, 256, 0, st>>>(sb);
+            }))
+            return rc;
     } else {
         const int per = 4 * (H / 16);
         const dim3 ggemm((2 * L - 1) * per, RB < OPNET_MAX_GY ? RB : OPNET_MAX_GY, 1);
@@ -2743,19 +2686,13 @@ extern "C" int opseq_lstm_stack_train_backward_f32(const float *dy, const float 
     if (dx0) {
         // dx0 [B*T][KX] = da0 [B*T][4H] . W_ih0 [4H][KX]  (k = 4*unit + gate on both sides) via the tiled GEMM
         float *rows = (float *)(w + W.darows);
-        const long nb = (long)B * T * H;
-        packed_da_to_rows<<<(unsigned)((nb + 255) / 256 > 8192 ? 8192 : (nb + 255) / 256), 256, 0, st>>>(
-            b.layer[0].g, rows, B, T, RB, H);
-        ConvArgs c = {};
-        c.X = rows; c.Wt = packed + TP.wih0_t; c.bias = nullptr; c.R = nullptr; c.Y = dx0;
-        c.N = 1; c.H = 1; c.W = B * T; c.Cin = 4 * H; c.Cout = KX; c.KH = 1; c.KW = 1; c.stride = 1; c.pad = 0;
-        c.OH = 1; c.OW = B * T; c.KP = 4 * H; c.relu = 0;
+        packed_da_to_rows<<<ew_blocks((long)B * T * H, 8192), 256, 0, st>>>(b.layer[0].g, rows, B, T, RB, H);
         const int M = B * T;
         // a short sequence (one clip: 3 x 2 tiles of 128 walking K = 4H alone, 160 us): 32 x 32 tiles, K split over the waves
         if (((M + 63) / 64) * ((KX + 63) / 64) < 256 && ((4 * H) & 15) == 0)
             gemm_bias_act_ks<<<dim3((M + 31) / 32, (KX + 31) / 32, 1), 256, 0, st>>>(rows, packed + TP.wih0_t, nullptr, dx0, M, KX, 4 * H, 0);
         else
-            launch_conv_tiled(c, M, st);
+            launch_conv_tiled(row_gemm_args(rows, packed + TP.wih0_t, nullptr, nullptr, dx0, M, KX, 4 * H, 0), M, st);
     }
     HIP_TRY(hipGetLastError());
     return OPNET_OK;
@@ -2982,10 +2919,7 @@ static int encoder_layer(float *z, const float *in_w, const float *in_b, const f
                 gemm_bias_act<<<dim3((M + 63) / 64, (N + 63) / 64, 1), 256, 0, st>>>(A, Wt, b, C, M, N, K, act);
             return OPNET_OK;
         }
-        ConvArgs c = {};
-        c.X = A; c.Wt = Wt; c.bias = b; c.R = nullptr; c.Y = C;
-        c.N = 1; c.H = 1; c.W = M; c.Cin = K; c.Cout = N; c.KH = 1; c.KW = 1; c.stride = 1; c.pad = 0;
-        c.OH = 1; c.OW = M; c.KP = K; c.relu = act;
+        const ConvArgs c = row_gemm_args(A, Wt, b, nullptr, C, M, N, K, act);
         if (batched) return launch_gemm_k256(c, M, st);     // (K = 256 products of a throughput pass: the resident-token tile, same bits)
         launch_conv_tiled(c, M, st);
         return OPNET_OK;
@@ -3220,13 +3154,11 @@ extern "C" int opdet_conv2d_wino_f32(const float *x, const float *u, const float
     for (long t0 = 0; t0 < tiles; t0 += ct) {
         const long NT = tiles - t0 < ct ? tiles - t0 : ct;
         const long ni = NT * (Cin / 4), no = NT * (Cout / 4);
-        wino_input<<<(unsigned)((ni + 255) / 256 > 16384 ? 16384 : (ni + 255) / 256), 256, 0, st>>>(x, V, t0, NT, H, W, Cin);
-        ConvArgs g = {};
-        g.X = V; g.Wt = u; g.Y = Mm;
-        g.N = 1; g.H = 1; g.W = (int)NT; g.Cin = Cin; g.Cout = Cout; g.KH = 1; g.KW = 1; g.stride = 1; g.pad = 0; g.OH = 1; g.OW = (int)NT; g.KP = Cin;
+        wino_input<<<ew_blocks(ni), 256, 0, st>>>(x, V, t0, NT, H, W, Cin);
+        ConvArgs g = row_gemm_args(V, u, nullptr, nullptr, Mm, NT, Cout, Cin, 0);
         g.bsx = NT * Cin; g.bsw = (long)Cout * Cin; g.bsy = NT * Cout;
         conv2d_nhwc_glds<64, 3><<<dim3((unsigned)((NT + 127) / 128), (Cout + 63) / 64, 16), 256, 0, st>>>(g);
-        wino_output<<<(unsigned)((no + 255) / 256 > 16384 ? 16384 : (no + 255) / 256), 256, 0, st>>>(Mm, bias, y, t0, NT, H, W, Cout, relu);
+        wino_output<<<ew_blocks(no), 256, 0, st>>>(Mm, bias, y, t0, NT, H, W, Cout, relu);
     }
     HIP_TRY(hipGetLastError());
     return OPNET_OK;

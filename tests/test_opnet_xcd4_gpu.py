@@ -184,12 +184,23 @@ def test_several_row_blocks_per_launch(B, T, monkeypatch):
     assert np.abs(y_i - y_j).max() < 2e-5 and np.abs(lg_i - lg_j).max() < 5e-5
 
 
+def _baseline_lstm():
+    from objectpermanence_amd import ModelsFactory
+    cfg = {"videos_hidden_dim": 512}
+    m = ModelsFactory.get_model("baseline_lstm", cfg)
+    m.load_state_dict({k: torch.from_numpy(v.copy()) for k, v in synth.baseline_lstm_synth_params(cfg).items()})
+    return m.to("cuda:0")
+
+
 def test_under_concurrent_load_and_mixed_with_the_16_clip_form():
     """A second stream keeps streaming kernels running while the persistent launches are resident; small (4-clip groups) and
-    large (16-clip groups) persistent forwards and a training step are issued from different streams - the library chains
-    every persistent launch of a device through one event, so no two of them are ever co-resident."""
+    large (16-clip groups) persistent forwards and a training step are issued from different streams, for OPNet and for the
+    stacked LSTM (BaselineLstm: seqx_forward, seqt_forward, and seqx_forward + seqx_backward in its training step) - the library
+    chains every persistent launch of a device through one event, so no two of them are ever co-resident and none aborts."""
     if not _supported():
         pytest.skip("needs a whole MI355X (8 XCDs x 32 CUs)")
+    from objectpermanence_amd import l1_mean
+    from objectpermanence_amd.launch_monitor import verify_launches
     small, labels = synth.make_batch(31, 24, 40)
     large, _ = synth.make_batch(32, 200, 40)
     m = _model().eval()
@@ -201,10 +212,20 @@ def test_under_concurrent_load_and_mixed_with_the_16_clip_form():
     m.train(True)
     _, y_t, _, g_t = _run(m, small, labels)
     xs, xl, lab = torch.from_numpy(small).cuda(), torch.from_numpy(large).cuda(), torch.from_numpy(labels).cuda()
-    big = torch.empty(64 << 20, dtype=torch.float32, device="cuda:0")
-    s1, s2, s3, s4 = (torch.cuda.Stream() for _ in range(4))
+    bl = _baseline_lstm()
+    bs, blg = torch.from_numpy(synth.boxes5(small)).cuda(), torch.from_numpy(synth.boxes5(large)).cuda()
+    assert bl._runner.engine(24, 40) == "x" and bl._runner.engine(200, 40) == "t"
+    with torch.no_grad():
+        yb_s, yb_l = bl(bs).cpu().numpy(), bl(blg).cpu().numpy()
+    yb_t = bl(bs)
+    l1_mean(yb_t, lab).backward()
     torch.cuda.synchronize()
-    from objectpermanence_amd import l1_mean
+    yb_t = yb_t.detach().cpu().numpy()
+    gb_t = {k: p.grad.cpu().numpy().copy() for k, p in bl.named_parameters()}
+    assert verify_launches(bl) == 0 and not bl.training_step_aborted()
+    big = torch.empty(64 << 20, dtype=torch.float32, device="cuda:0")
+    s1, s2, s3, s4, s5, s6, s7 = (torch.cuda.Stream() for _ in range(7))
+    torch.cuda.synchronize()
     outs = []
     for it in range(3):
         with torch.cuda.stream(s3):
@@ -216,18 +237,32 @@ def test_under_concurrent_load_and_mixed_with_the_16_clip_form():
                 outs.append(("small", m(xs)[0]))
             with torch.cuda.stream(s2):
                 outs.append(("large", m(xl)[0]))
+            with torch.cuda.stream(s5):
+                outs.append(("lstm small", bl(bs)))
+            with torch.cuda.stream(s6):
+                outs.append(("lstm large", bl(blg)))
         m.train(True)
         with torch.cuda.stream(s4):
             m.zero_grad(set_to_none=True)
             yt, _ = m(xs)
             l1_mean(yt, lab).backward()
             outs.append(("train", yt.detach()))
+        with torch.cuda.stream(s7):
+            bl.zero_grad(set_to_none=True)
+            yt = bl(bs)
+            l1_mean(yt, lab).backward()
+            outs.append(("lstm train", yt.detach()))
     torch.cuda.synchronize()
+    # (the monitors would re-run an aborted forward on the launch chain and hide an overlap)
+    for model in (m, bl):
+        assert verify_launches(model) == 0 and not model.training_step_aborted()
     for name, y in outs:
-        ref = {"small": y_s, "large": y_l, "train": y_t}[name]
+        ref = {"small": y_s, "large": y_l, "train": y_t, "lstm small": yb_s, "lstm large": yb_l, "lstm train": yb_t}[name]
         assert np.array_equal(y.cpu().numpy(), ref), name
     for k, p in m.named_parameters():
         assert np.array_equal(p.grad.cpu().numpy(), g_t[k]), k
+    for k, p in bl.named_parameters():
+        assert np.array_equal(p.grad.cpu().numpy(), gb_t[k]), k
 
 
 def test_a_stuck_exchange_aborts_with_nan_and_the_next_launch_is_clean(monkeypatch):
