@@ -270,6 +270,21 @@ int opnet_stream_step_f32(const float *boxes, const int32_t *slots, float *state
 int opnet_stream_step_ragged_f32(const float *boxes, const int32_t *slots, const int32_t *lengths, float *state,
                                  const float *packed, float *y, float *logits, void *workspace, size_t workspace_bytes, int n,
                                  int k, int capacity, int H1, int H2, int mlp, void *stream);
+/* The uniform OPNet step (not OPNetLstmMlp) as ONE persistent launch of the 4-clip form (opnet_xcd4_forward_f32) that reads
+ * each named stream's state from the pool and writes it back: reference hidden sizes on a whole MI355X
+ * (opnet_xcd_supported), n <= opnet_stream_x4_max_streams() streams a call.  x4packed is the image of
+ * opnet_xcd4_pack_weights_f32; every other argument, check and error code as opnet_stream_step_f32.  Four dependent
+ * launches whatever k.  Each frame has the arithmetic of opnet_xcd4_forward_f32 over the same n clips: any chunking of a
+ * clip's frames into such calls gives the bits of that whole-clip forward (which differ from the launch chain's in the
+ * last places; both are fp32).  A state word with the bits 0xffffffff (a NaN) is read as the NaN 0x7fc00000.  A pool row may be advanced by either entry in any order.  The launch's status words lie at
+ * opnet_stream_x4_status_offset(...) of the workspace; if it gave up (word 0 != 0) the named pool rows are left as they were
+ * before the call and y / logits are NaN, so the caller can run the same call again through opnet_stream_step_f32. */
+int    opnet_stream_x4_max_streams(void);                                 /* = opnet_xcd4_max_batch() */
+size_t opnet_stream_x4_workspace_bytes(int n, int k, int H1, int H2);     /* 0: not served (sizes, n, or > 2 GiB) */
+size_t opnet_stream_x4_status_offset(int n, int k, int H1, int H2);       /* (size_t)-1: not served */
+int    opnet_stream_step_x4_f32(const float *boxes, const int32_t *slots, float *state, const float *x4packed,
+                                float *y, float *logits, void *workspace, size_t workspace_bytes,
+                                int n, int k, int capacity, int H1, int H2, void *stream);
 
 /* L (1..3) stacked bias-free LSTM layers (input width KX, hidden H each) + Linear H->4:
  *   x [B,T,KX] -> y [B,T,4].  BaselineLstm (:92-118): L=1, KX=75.  NonLinearLstm (:121-151): L=2,

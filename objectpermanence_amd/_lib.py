@@ -119,6 +119,15 @@ def _declare(lib):
     lib.opnet_stream_step_ragged_f32.restype = c_int
     lib.opnet_stream_step_ragged_f32.argtypes = [fp, fp, fp, fp, fp, fp, fp, c_void_p, c_size_t, c_int, c_int, c_int, c_int,
                                                  c_int, c_int, c_void_p]
+    lib.opnet_stream_x4_max_streams.restype = c_int
+    lib.opnet_stream_x4_max_streams.argtypes = []
+    lib.opnet_stream_x4_workspace_bytes.restype = c_size_t
+    lib.opnet_stream_x4_workspace_bytes.argtypes = [c_int, c_int, c_int, c_int]
+    lib.opnet_stream_x4_status_offset.restype = c_size_t
+    lib.opnet_stream_x4_status_offset.argtypes = [c_int, c_int, c_int, c_int]
+    lib.opnet_stream_step_x4_f32.restype = c_int
+    lib.opnet_stream_step_x4_f32.argtypes = [fp, fp, fp, fp, fp, fp, c_void_p, c_size_t, c_int, c_int, c_int, c_int, c_int,
+                                             c_void_p]
     lib.opnet_online_encode_f32.restype = c_int
     lib.opnet_online_encode_f32.argtypes = [fp, fp, fp, fp, c_int, fp, fp, c_int, fp, c_int, c_int, c_int, c_int, c_float, fp,
                                             c_void_p]
@@ -332,6 +341,8 @@ EXPORTS = [
     "opnet_adam_multi_step_guarded_f32", "opnet_dp_guard_f32", "opnet_xcd4_status_offset", "opnet_train_status_offset", "opnet_xcd4_enable", "opnet_xcd4_enabled",
     "opnet_mlp_pack_weights_f32", "opnet_mlp_forward_f32",
     "opnet_stream_state_floats", "opnet_stream_workspace_bytes", "opnet_stream_step_f32", "opnet_stream_step_ragged_f32",
+    "opnet_stream_x4_max_streams", "opnet_stream_x4_workspace_bytes", "opnet_stream_x4_status_offset",
+    "opnet_stream_step_x4_f32",
     "opnet_online_encode_f32", "opnet_online_encode_ragged_f32",
     "opnet_mlp_train_pack_weights_f32", "opnet_mlp_train_forward_f32", "opnet_mlp_train_backward_f32",
     "opseq_lstm_stack_packed_bytes", "opseq_lstm_stack_workspace_bytes", "opseq_lstm_stack_pack_weights_f32",

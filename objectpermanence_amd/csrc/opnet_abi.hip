@@ -15,6 +15,7 @@
 #include "enc_train_kernels.hip"
 #include "attn_train_kernels.hip"
 #include "opnet_stream_kernels.hip"
+#include "opnet_stream_x4_kernels.hip"
 #include "seq_stream_kernels.hip"
 #include "online_encode_kernels.hip"
 

@@ -87,6 +87,8 @@ struct Xcd4Args {
     int force_safe;
     int debug;                 // tools only (wrong results): bit 0 no gather, 1 no history stores, 2 no cells, 3 no head, 4 no products
     unsigned long long *trace; // optional [phases][8] s_memtime stamps of block 0, wave 0
+    unsigned cs1_off, cs2_off; // opnet_xcd4_forward<false, true> (stream steps) only: the cell states in and out,
+                               // [RB*8 groups][H units][4 clips] float = the sC1 / sC2 entries of every (group, CU), CU by CU
 };
 
 typedef float x4_f32x4 __attribute__((ext_vector_type(4)));
@@ -300,9 +302,16 @@ __device__ __forceinline__ float x4_row_shl(float v)
     return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x100 + N, 0xf, 0xf, true));
 }
 
-template <bool TRAIN>
+// STATE (inference only; opnet_stream_step_x4_f32): the launch continues streams instead of starting clips.  h1 / h2 of the step
+// before the first are whatever the launch in front put into ring slot 0 (opnet_stream_x4_prologue); c1 / c2 are loaded from
+// cs1 / cs2 in place of the zero fill and stored back once behind the phase loop.  Nothing between differs.  Both directions cross
+// a kernel boundary (the prologue's stores -> this launch, this launch's stores -> opnet_stream_x4_writeback), which is what makes
+// plain stores of workgroups on other XCDs visible - the way opnet_xcd4_init fills the rings and opnet_xcd4_out_head reads the h2
+// history; nothing is fenced inside the loop.
+template <bool TRAIN, bool STATE = false>
 __global__ void __launch_bounds__(256) opnet_xcd4_forward(const Xcd4Args a)
 {
+    static_assert(!(TRAIN && STATE), "the training forward starts every clip from the zero state");
     // Phase (row block gi, step s), T + 2 steps:  LSTM1 step s | selection head step s-1 | LSTM2 step s-2.
     //   CU c: LSTM2 64 gate rows x K = 512 split over the 4 waves (128 VGPRs a wave), LSTM1 32 gate rows x K = 96 + 256 (44),
     //   the selection head (every CU, redundantly) 16 rows x K = 256 (16), wave 0: W_ih2 of its 64 rows (8).
@@ -337,8 +346,19 @@ __global__ void __launch_bounds__(256) opnet_xcd4_forward(const Xcd4Args a)
             if (loc == 0 && c == 0) atomicAdd(a.status + 3, 1u);
         }
     }
-    for (int i = tid; i < X4_NGMAX * 64; i += 256) (&sC2[0][0])[i] = 0.f;
-    for (int i = tid; i < X4_NGMAX * 32; i += 256) { (&sC1[0][0])[i] = 0.f; (&sFB[0][0][0])[i] = 0.f; }
+    if (STATE) {
+        // this CU's (group gi * 8 + x, units of CU c) entries: sC2 lane = 4 b + j = 4 (unit - 16 c) + clip, sC1 likewise with 8 c
+        const float *cs2 = (const float *)(a.ws + a.cs2_off), *cs1 = (const float *)(a.ws + a.cs1_off);
+        for (int i = tid; i < X4_NGMAX * 64; i += 256)
+            (&sC2[0][0])[i] = (i >> 6) < ng ? cs2[((size_t)((i >> 6) * 8 + x) * 32 + c) * 64 + (i & 63)] : 0.f;
+        for (int i = tid; i < X4_NGMAX * 32; i += 256) {
+            (&sC1[0][0])[i] = (i >> 5) < ng ? cs1[((size_t)((i >> 5) * 8 + x) * 32 + c) * 32 + (i & 31)] : 0.f;
+            (&sFB[0][0][0])[i] = 0.f;
+        }
+    } else {
+        for (int i = tid; i < X4_NGMAX * 64; i += 256) (&sC2[0][0])[i] = 0.f;
+        for (int i = tid; i < X4_NGMAX * 32; i += 256) { (&sC1[0][0])[i] = 0.f; (&sFB[0][0][0])[i] = 0.f; }
+    }
 
     // ---- resident weights ------------------------------------------------------------------------------------------------
     const X4Packed P = x4_packed_layout();
@@ -642,6 +662,17 @@ __global__ void __launch_bounds__(256) opnet_xcd4_forward(const Xcd4Args a)
         abort_seen = XCD_LDS_LD(sAbort);
         gi = gn;
         s = sn;
+    }
+    if (STATE) {
+        // the cell waves hand their c back, each lane the entries it alone has written (no barrier needed); a launch that gave up
+        // may leave anything here: the write-back looks at status[0] before it touches a pool row
+        if (w == 0) {
+            float *cs2 = (float *)(a.ws + a.cs2_off);
+            for (int g = 0; g < ng; ++g) cs2[((size_t)(g * 8 + x) * 32 + c) * 64 + lane] = sC2[g][lane];
+        } else if (w == 1 && lane < 32) {
+            float *cs1 = (float *)(a.ws + a.cs1_off);
+            for (int g = 0; g < ng; ++g) cs1[((size_t)(g * 8 + x) * 32 + c) * 32 + lane] = sC1[g][lane];
+        }
     }
 }
 

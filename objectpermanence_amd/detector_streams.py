@@ -25,6 +25,10 @@ Streams may advance by different numbers of frames in one call: `lengths` ([n], 
 list of per-stream frame arrays [k_i, H, W, 3] for step.  Frames past a stream's length are padding: they count as frames
 without detections for the encoder (nothing is learned from them, they encode as zeros) and never reach the pool's state.
 
+A backlog of many frames can run as one persistent launch instead of the launch chain: `DetectorStreams(..., engine=)` sets the
+OPNet pool's default engine, `step(..., engine=)` / `step_detections(..., engine=)` choose per call (streaming.OPNetStreams;
+uniform calls only, refused for the stacked reasoners); `verify_launches()` at a sync point, as on the pool.
+
 `encode_detections_numpy` is the readable statement the kernel is held to bit for bit, as encode_boxes is to the native
 clip encoder.  step_detections and encode do not synchronise the host: slot ids go up through fresh pinned buffers, and
 nothing comes back down.
@@ -40,7 +44,7 @@ from . import _lib
 from .datasets import FRAME_SHAPES, MAX_OBJECTS, _cone_table
 from .learned_models import BaselineLstm, NonLinearLstm, OPNet, OPNetLstmMlp, _stream_ptr
 from .object_indices import SNITCH_INDEX
-from .streaming import LstmStackStreams, OPNetStreams, call_entry, upload_async
+from .streaming import LstmStackStreams, OPNetStreams, call_entry, check_engine, upload_async
 
 TABLE_INTS = 16                # OPNET_ONLINE_TABLE_INTS: 15 class ids + the mode
 MODE_FIXED, MODE_LEARNED = 0, 1
@@ -172,10 +176,13 @@ class DetectorStreams:
     stream.  Calls are enqueued on the current torch stream and are inference only."""
 
     def __init__(self, model, detector=None, capacity: int = 1024, score_thresh: float = SCORE_THRESHOLD,
-                 n_tracks: Optional[int] = None):
+                 n_tracks: Optional[int] = None, engine: str = "chain"):
         if isinstance(model, (OPNet, OPNetLstmMlp)):
-            pool, tracks = OPNetStreams(model, capacity), 6
+            pool, tracks = OPNetStreams(model, capacity, engine=engine), 6
         elif isinstance(model, (BaselineLstm, NonLinearLstm)):
+            if check_engine(engine) != "chain":
+                raise ValueError(f"engine={engine!r} is served for OPNet only: {type(model).__name__} streams "
+                                 "(LstmStackStreams) run on the launch chain")
             pool, tracks = LstmStackStreams(model, capacity), 5
         else:
             raise TypeError(f"DetectorStreams serves OPNet, OPNetLstmMlp, BaselineLstm and NonLinearLstm, not "
@@ -281,26 +288,46 @@ class DetectorStreams:
         return self._encode(ids, boxes, scores, labels, n_det, lengths)[2]
 
     # -- frames -------------------------------------------------------------------------------
+    def verify_launches(self) -> int:
+        """as OPNetStreams.verify_launches: wait for the model's persistent launches, heal a step that gave up"""
+        if isinstance(self.pool, OPNetStreams):
+            return self.pool.verify_launches()
+        return 0
+
+    def _check_engine(self, engine, lengths) -> None:
+        """before anything is encoded: an engine the pool refuses must not leave the slot tables half updated"""
+        self.pool._check_engine(engine, lengths)
+
     def _advance(self, slots: torch.Tensor, x: torch.Tensor, detections,
-                 lengths: Optional[torch.Tensor] = None) -> StreamResult:
+                 lengths: Optional[torch.Tensor] = None, engine: Optional[str] = None) -> StreamResult:
         n, k = int(x.shape[0]), int(x.shape[1])
         with torch.no_grad(), torch.cuda.device(self.device):
-            out = self.pool._step_slots(slots, x, lengths)
+            out = self.pool._step_slots(slots, x, lengths, engine=engine)
             y, logits = out if isinstance(out, tuple) else (out, None)
             px = torch.empty((n, k, 4), dtype=torch.int32, device=self.device)
-            rc = _lib.load().opnet_postprocess_iou(y.data_ptr(), None, px.data_ptr(), None, None, n, k,
-                                                   _stream_ptr(self.device))
-            _lib.check(rc, "opnet_postprocess_iou")
+
+            def pixels():
+                with torch.cuda.device(self.device):
+                    rc = _lib.load().opnet_postprocess_iou(y.data_ptr(), None, px.data_ptr(), None, None, n, k,
+                                                           _stream_ptr(self.device))
+                _lib.check(rc, "opnet_postprocess_iou")
+            pixels()
+            # y of an unverified persistent step (and of every step behind it) may still be rewritten by the pool's replay:
+            # the pixel boxes are then derived again, into the px the caller holds
+            if isinstance(self.pool, OPNetStreams):
+                self.pool.log_followup(pixels)
         return StreamResult(px, y, logits, x, detections, lengths)
 
     def step_detections(self, ids: Sequence[int], boxes: torch.Tensor, scores: torch.Tensor, labels: torch.Tensor,
-                        n_det: torch.Tensor, lengths=None) -> StreamResult:
+                        n_det: torch.Tensor, lengths=None, engine: Optional[str] = None) -> StreamResult:
         """encode k frames of detections of your own detector (as `encode`) and advance the streams by them (stream i by
-        its first lengths[i] when lengths are given).  No host sync."""
+        its first lengths[i] when lengths are given).  engine: "chain" or "persistent" (OPNet pools, uniform calls) for this
+        call, None = the pool's default.  No host sync."""
+        self._check_engine(engine, lengths)
         slots, lens, x = self._encode(ids, boxes, scores, labels, n_det, lengths)
-        return self._advance(slots, x, (boxes, scores, labels, n_det), lens)
+        return self._advance(slots, x, (boxes, scores, labels, n_det), lens, engine)
 
-    def step(self, ids: Sequence[int], frames) -> StreamResult:
+    def step(self, ids: Sequence[int], frames, engine: Optional[str] = None) -> StreamResult:
         """k frames per stream through the detector, the encoder and the pool: frames uint8 BGR [n, k, H, W, 3] (row i
         belongs to ids[i]; one shape for all).  The detector runs in passes of at most MAX_FRAMES_PER_PASS frames in
         stream-major order (whole streams per pass when k allows it), the encoder once per pass into its slice of x.
@@ -313,7 +340,9 @@ class DetectorStreams:
         if self.detector is None:
             raise RuntimeError("DetectorStreams.step needs a detector: DetectorStreams(model, detector=...)")
         if isinstance(frames, (list, tuple)):
-            return self._step_ragged(ids, frames)
+            self._check_engine(engine, frames)
+            return self._step_ragged(ids, frames, engine)
+        self._check_engine(engine, None)
         frames = np.asarray(frames)
         if frames.dtype != np.uint8 or frames.ndim != 5 or frames.shape[4] != 3 or frames.shape[1] < 1:
             raise ValueError(f"frames must be uint8 [n, k>=1, H, W, 3], got {frames.dtype} {tuple(frames.shape)}")
@@ -340,9 +369,9 @@ class DetectorStreams:
                                   l.view(*shape, md), nd.view(*shape))
                 parts.append((b, s, l, nd))
             det = tuple(torch.cat([p[q] for p in parts]).view(n, k, *parts[0][q].shape[1:]) for q in range(4))
-        return self._advance(slots, x, det)
+        return self._advance(slots, x, det, None, engine)
 
-    def _step_ragged(self, ids: Sequence[int], frames) -> StreamResult:
+    def _step_ragged(self, ids: Sequence[int], frames, engine: Optional[str] = None) -> StreamResult:
         idx = self.pool.slots.check(ids)
         n = idx.size
         if len(frames) != n:
@@ -379,4 +408,4 @@ class DetectorStreams:
             boxes, scores, labels, n_det = det
             x = torch.empty((n, K, MAX_OBJECTS, self.n_tracks), dtype=torch.float32, device=self.device)
             self._encode_into(x, slots, boxes, scores, labels, n_det, lens)
-        return self._advance(slots, x, (boxes, scores, labels, n_det), lens)
+        return self._advance(slots, x, (boxes, scores, labels, n_det), lens, engine)

@@ -48,6 +48,11 @@ class LaunchMonitor:
     def pending(self) -> int:
         return len(self._pending)
 
+    def watching(self, redo: Callable[[], None]) -> bool:
+        """is a launch that was watched with this very `redo` still pending?  (After `reap`: still running, or aborted and
+        waiting for `verify`.)  The stream pools ask this to know how much of their replay log they still need."""
+        return any(entry[2] is redo for entry in self._pending)
+
     def reap(self) -> int:
         """drop every watched launch that has completed with clean status words - without waiting for any (event.query()) -
         and with it the reference to its input that `redo` holds; an aborted one stays for `verify` to heal.  Returns how

@@ -302,15 +302,21 @@ class OPNet(AbstractCaterModel):
             self._xcd_ok = bool(_lib.load().opnet_xcd_supported(self._h1, self._h2))
         return self._xcd_ok
 
+    def _x4_packed_weights(self, device: torch.device, stream: int) -> torch.Tensor:
+        """the 4-clip persistent kernels' weight image (opnet_xcd4_pack_weights_f32) for launches on `stream`; shared by
+        _forward_xcd4 and the persistent engine of streaming.OPNetStreams"""
+        lib = _lib.load()
+        ws_ = self._weights()
+        return self._x4packed.get(
+            stream, ws_, device, (lib.opnet_xcd4_packed_weights_bytes, self._h1, self._h2), lambda buf, n: _lib.check(
+                lib.opnet_xcd4_pack_weights_f32(*(w.data_ptr() for w in ws_), buf.data_ptr(), n, self._h1, self._h2, stream),
+                "opnet_xcd4_pack_weights_f32"))
+
     def _forward_xcd4(self, boxes: torch.Tensor, stream: int):
         """up to 32 clips as ONE persistent launch of 4-clip groups, one per XCD (csrc/opnet_xcd4_kernels.hip)"""
         lib = _lib.load()
         B, T, dev = int(boxes.shape[0]), int(boxes.shape[1]), boxes.device
-        ws_ = self._weights()
-        x4packed = self._x4packed.get(
-            stream, ws_, dev, (lib.opnet_xcd4_packed_weights_bytes, self._h1, self._h2), lambda buf, n: _lib.check(
-                lib.opnet_xcd4_pack_weights_f32(*(w.data_ptr() for w in ws_), buf.data_ptr(), n, self._h1, self._h2, stream),
-                "opnet_xcd4_pack_weights_f32"))
+        x4packed = self._x4_packed_weights(dev, stream)
         ws = self._x4ws.get(stream, (B, T), dev, (lib.opnet_xcd4_workspace_bytes, B, T, self._h1, self._h2))
         y = torch.empty((B, T, 4), dtype=torch.float32, device=dev)
         logits = torch.empty((B, 15, T), dtype=torch.float32, device=dev)

@@ -27,17 +27,27 @@ boxes[i, :lengths[i]], the rest of its row is padding that never reaches the sta
 (opnet_stream_step_ragged_f32 / opseq_stream_step_ragged_f32).  One call then serves a tick in which the streams have
 different numbers of new frames, with the bits of the uniform call over the same streams on every valid frame.
 
+A call that carries many frames (a backlog, a video decoded in pieces, a restored checkpoint fast-forwarded) is better served
+by ONE persistent launch than by k + 5 dependent ones: `OPNetStreams(model, capacity, engine="persistent")`, or
+`step(ids, boxes, engine="persistent")` for one call (opnet_stream_step_x4_f32: the 4-clip persistent forward, reading each
+stream's state from the pool and writing it back; OPNet at the reference hidden sizes on a whole MI355X, uniform calls only).
+Both engines work on the same pool rows, so a stream can be warmed up on one and ticked on the other.  Each engine is
+chunk-invariant on its own; the two round differently in the last places, which is why the engine is always the caller's
+choice and never a function of k.  Persistent steps are watched by the model's LaunchMonitor: call `verify_launches()` at a
+sync point before trusting outputs on the host, as after `model(boxes)`.
+
 TransformerLstm is not streamed: its encoder attends over the whole sequence, so a frame's output depends on later frames.
 """
 from __future__ import annotations
 
-from typing import List, Optional, Sequence
+from typing import Callable, List, Optional, Sequence
 
 import numpy as np
 import torch
 
 from . import _lib
 from ._device_cache import Workspaces
+from .launch_monitor import verify_launches
 from .learned_models import BaselineLstm, NonLinearLstm, OPNet, OPNetLstmMlp, _stream_ptr
 
 
@@ -108,6 +118,83 @@ def upload_async(a: np.ndarray, device) -> torch.Tensor:
     return torch.from_numpy(np.ascontiguousarray(a)).pin_memory().to(device, non_blocking=True)
 
 
+ENGINES = ("chain", "persistent")
+
+
+def check_engine(engine, default: Optional[str] = None) -> str:
+    """`engine` as one of ENGINES (None: `default`, where a default exists), or an exception"""
+    if engine is None and default is not None:
+        return default
+    if not isinstance(engine, str):
+        raise TypeError(f"engine must be one of {ENGINES}, got {type(engine).__name__}")
+    if engine not in ENGINES:
+        raise ValueError(f"engine must be one of {ENGINES}, got {engine!r} (there is no automatic choice: the two engines "
+                         "round differently, so which one runs is never decided behind the caller's back)")
+    return engine
+
+
+class ReplayEntry:
+    """one logged call: the pool rows it names (`slots`), their contents before it (`before`), what is needed to run it
+    again (`payload`), and - for a watched persistent launch - the `redo` its monitor holds"""
+    __slots__ = ("slots", "before", "payload", "redo", "healed")
+
+    def __init__(self, slots, before, payload):
+        self.slots, self.before, self.payload = slots, before, payload
+        self.redo: Optional[Callable[[], None]] = None
+        self.healed = False
+
+
+class StreamReplayLog:
+    """The undo / redo log of a stream pool, kept while a persistent step of the pool is unverified.
+
+    A whole-clip forward that gave up is healed by running it again; a stream step has a past: by the time the host learns
+    that call i gave up, calls i+1 .. m have already advanced the pool from the state call i left behind.  A step that gave
+    up leaves its own rows as they were (opnet_stream_x4_writeback), so undoing calls m .. i+1 - newest first, each putting
+    back the rows it named as they were before it - gives exactly the pool before call i; calls i .. m are then run again in
+    order through the launch chain, into the output tensors the caller already holds.
+
+    `restore(slots, before)` puts rows back; `rerun(payload)` runs a logged call again (on the chain).  Both are the
+    pool's; the log itself only keeps order, so it is tested on the host with numpy."""
+
+    def __init__(self, restore: Callable, rerun: Callable):
+        self._restore, self._rerun = restore, rerun
+        self.entries: List[ReplayEntry] = []
+
+    def __len__(self) -> int:
+        return len(self.entries)
+
+    def record(self, slots, before, payload) -> ReplayEntry:
+        entry = ReplayEntry(slots, before, payload)
+        self.entries.append(entry)
+        return entry
+
+    def prune(self, unverified: Callable[[ReplayEntry], bool]) -> None:
+        """drop every entry in front of the oldest one whose launch is still `unverified` (all of them when none is): an
+        abort found later can only rewind to that entry"""
+        for i, entry in enumerate(self.entries):
+            if entry.redo is not None and not entry.healed and unverified(entry):
+                del self.entries[:i]
+                return
+        self.entries.clear()
+
+    def replay(self, entry: ReplayEntry) -> int:
+        """rewind the pool to the state before `entry` and run it and every later logged call again; returns how many
+        calls were run.  An entry that an earlier replay has already run again (or that was pruned) is left alone."""
+        if entry.healed or not any(e is entry for e in self.entries):
+            return 0
+        i = next(j for j, e in enumerate(self.entries) if e is entry)
+        todo = self.entries[i:]
+        for e in reversed(todo):
+            self._restore(e.slots, e.before)
+        for e in todo:
+            self._rerun(e.payload)
+            e.healed = True
+        return len(todo)
+
+    def clear(self) -> None:
+        self.entries.clear()
+
+
 def call_entry(entry: str, args: list, lengths: Optional[torch.Tensor], at: int) -> None:
     """the C entry `entry` (a `..._f32` of include/opnet_hip.h) on args, or for a ragged call (lengths given) its
     `..._ragged_f32` twin, which takes the lengths pointer at position `at` of the same argument list"""
@@ -157,11 +244,13 @@ class _StreamPool:
         self.slots.close(ids)
 
     # -- frames -------------------------------------------------------------------------------
-    def step(self, ids: Sequence[int], x: torch.Tensor, lengths=None):
+    def step(self, ids: Sequence[int], x: torch.Tensor, lengths=None, engine: Optional[str] = None):
         """advance the streams `ids` by k frames: x [n, k, S, F] (row i belongs to ids[i]) -> the outputs of those frames
         (OPNetStreams: boxes [n, k, 15, 6] -> (y [n, k, 4], logits [n, 15, k]); LstmStackStreams: x [n, k, 15, 5] ->
         y [n, k, 4]).  lengths ([n] ints in 0..k, on the host or an int32 device tensor): stream i advances by its first
-        lengths[i] frames only; the outputs are +0.0 on the others."""
+        lengths[i] frames only; the outputs are +0.0 on the others.  engine (OPNetStreams): "chain" or "persistent" for
+        this call, None = the pool's default."""
+        self._check_engine(engine, lengths)
         name = self._frames
         if not isinstance(x, torch.Tensor) or not x.is_cuda:
             raise RuntimeError(f"{type(self).__name__}.step runs on MI355X only: `{name}` must be a tensor on a ROCm device")
@@ -173,7 +262,13 @@ class _StreamPool:
         if x.dim() != 4 or x.shape[0] != n or x.shape[2] != S or x.shape[3] != F or x.shape[1] < 1:
             raise ValueError(f"{name} must be [n={n}, k>=1, {S}, {F}], got {tuple(x.shape)}")
         slots, lens = self._device_ids(idx, lengths, int(x.shape[1]))
-        return self._step_slots(slots, x, lens)
+        return self._step_slots(slots, x, lens, engine=engine)
+
+    def _check_engine(self, engine, lengths) -> None:
+        """a pool with one engine takes no `engine` (OPNetStreams overrides this)"""
+        if engine is not None and check_engine(engine) != "chain":
+            raise ValueError(f"{type(self).__name__} has one engine, the launch chain: engine={engine!r} is served by "
+                             "OPNetStreams only")
 
     def _device_ids(self, idx: np.ndarray, lengths, k: int):
         """(slots, lengths) on the device for a call of k frames: the uniform call (lengths None) uploads the slot ids as
@@ -199,7 +294,7 @@ class OPNetStreams(_StreamPool):
     in-place parameter update takes effect on the next call."""
     _frames, _frames_are, _frame_shape = "boxes", "boxes are", (15, 6)
 
-    def __init__(self, model, capacity: int = 1024):
+    def __init__(self, model, capacity: int = 1024, engine: str = "chain"):
         if isinstance(model, OPNet):
             self._mlp = 0
         elif isinstance(model, OPNetLstmMlp):
@@ -208,9 +303,56 @@ class OPNetStreams(_StreamPool):
             raise TypeError(f"OPNetStreams serves OPNet and OPNetLstmMlp, not {type(model).__name__} (BaselineLstm and "
                             "NonLinearLstm are streamed by LstmStackStreams; transformer_lstm is not streamed: its encoder "
                             "attends over the whole sequence)")
+        engine = check_engine(engine)
+        if engine == "persistent" and self._mlp:
+            raise TypeError(self._NO_MLP)
         super().__init__(model, capacity)
         self.H1, self.H2 = model._h1, model._h2
         self._alloc_state(_lib.load().opnet_stream_state_floats(self.H1, self.H2), "opnet_stream_state_floats")
+        self._x4ws = Workspaces(8)
+        self._x4_ok: Optional[bool] = None
+        self._gave_up = False
+        self._log = StreamReplayLog(self._restore_rows, self._rerun)
+        self.healed_calls = 0            # calls run again on the chain after a persistent step gave up
+        self.engine = "chain"
+        if engine == "persistent":
+            self._check_persistent()
+            self.engine = engine
+
+    _NO_MLP = ("engine='persistent' serves OPNet only: OPNetLstmMlp has no persistent kernel (its streams run on the "
+               "launch chain)")
+
+    # -- engines ------------------------------------------------------------------------------
+    def _check_persistent(self) -> None:
+        """the preconditions of the persistent engine, or an exception"""
+        if self._mlp:
+            raise TypeError(self._NO_MLP)
+        if self._gave_up:
+            raise RuntimeError("a persistent step of this pool gave up earlier and was healed on the launch chain; the pool "
+                               "stays on engine='chain'")
+        if self._x4_ok is None:
+            with torch.cuda.device(self.device):
+                self._x4_ok = bool(_lib.load().opnet_xcd_supported(self.H1, self.H2))
+        if not self._x4_ok:
+            raise ValueError(f"engine='persistent' needs the reference hidden sizes (256, 512) on a whole MI355X (8 XCDs x 32 "
+                             f"CUs visible); this pool has H1={self.H1}, H2={self.H2} on {self.device}: use engine='chain'")
+
+    def _check_engine(self, engine, lengths) -> None:
+        if check_engine(engine, self.engine) != "persistent":
+            return
+        self._check_persistent()
+        if lengths is not None:
+            raise ValueError("engine='persistent' takes uniform calls only: ragged persistent steps are not built "
+                             "(pass lengths with engine='chain')")
+
+    def verify_launches(self) -> int:
+        """wait for the persistent steps (and forwards) of the model issued so far; a step that gave up is healed: the pool
+        is rewound to the state before it, that call and every later one run again on the launch chain into the tensors they
+        returned, and the pool stays on the chain.  Returns the number of launches that gave up.  Call it at the sync point
+        you already have, before anything reads a persistent step's outputs on the host."""
+        n = verify_launches(self.model)
+        self._prune_log()
+        return n
 
     # -- state --------------------------------------------------------------------------------
     def get_state(self, ids: Sequence[int]):
@@ -251,25 +393,152 @@ class OPNetStreams(_StreamPool):
             if self._mlp:      # leave the h2 / c2 columns as they are
                 self.state[:, :2 * self.H1].index_copy_(0, dst, torch.cat(cols, dim=1))
             else:
-                self.state.index_copy_(0, dst, torch.cat(cols, dim=1))
+                rows = torch.cat(cols, dim=1)
+                self._log_write(dst, rows)
+                self.state.index_copy_(0, dst, rows)
+
+    def open(self, count: int = 1) -> List[int]:
+        ids = super().open(count)
+        if len(self._log):       # a replay must zero the rows again
+            with torch.cuda.device(self.device):
+                dst = torch.tensor(ids, dtype=torch.int64).to(self.device)
+                self._log.record(dst, torch.zeros((len(ids), self._row), dtype=torch.float32, device=self.device),
+                                 ("rows", dst, None))
+        return ids
+
+    # -- the replay log (StreamReplayLog) -----------------------------------------------------------
+    def _prune_log(self) -> None:
+        if len(self._log):
+            mon = self.model._monitor
+            mon.reap()
+            self._log.prune(lambda e: mon.watching(e.redo))
+
+    def _log_write(self, dst: torch.Tensor, rows: torch.Tensor) -> None:
+        """a set_state while the log is kept: a replay has to repeat it"""
+        self._prune_log()
+        if len(self._log):
+            self._log.record(dst, self.state.index_select(0, dst), ("rows", dst, rows.clone()))
+
+    def log_followup(self, fn: Callable[[], None]) -> None:
+        """device work a caller derived from the outputs of the step it has just made (DetectorStreams: the pixel boxes of
+        y): while the log is kept it is recorded behind that step, so that a replay which rewrites the step's outputs runs
+        `fn()` again - into the same tensors, which is `fn`'s business.  Names no pool rows."""
+        if len(self._log):
+            self._log.record(self.state.new_empty(0, dtype=torch.int64), self.state[:0], ("call", fn))
+
+    def _restore_rows(self, slots: torch.Tensor, before: torch.Tensor) -> None:
+        self.state.index_copy_(0, slots.long(), before)
+
+    def _rerun(self, payload) -> None:
+        if payload[0] == "call":         # work derived from a step's outputs (log_followup)
+            payload[1]()
+            return
+        if payload[0] == "rows":
+            _, dst, rows = payload
+            if rows is None:
+                self.state.index_fill_(0, dst, 0.0)
+            else:
+                self.state.index_copy_(0, dst, rows)
+            return
+        _, slots, boxes, lengths, y, logits = payload
+        self._step_chain(slots, boxes, lengths, (y, logits))
+        self.healed_calls += 1
+
+    def _heal(self, entry: ReplayEntry) -> None:
+        """the monitor's redo of a persistent step that gave up"""
+        if entry.healed:
+            return               # run again already, behind an earlier step that gave up
+        with torch.no_grad(), torch.cuda.device(self.device):
+            self.engine, self._gave_up = "chain", True     # for good: a later engine="persistent" is refused
+            # the later calls of the log may still be running, on other streams too: the rows are put back behind all of them
+            torch.cuda.synchronize(self.device)
+            self._log.replay(entry)
+            self._log.clear()
 
     # -- frames -------------------------------------------------------------------------------
-    def _step_slots(self, slots: torch.Tensor, boxes: torch.Tensor, lengths: Optional[torch.Tensor] = None):
+    def _step_slots(self, slots: torch.Tensor, boxes: torch.Tensor, lengths: Optional[torch.Tensor] = None,
+                    engine: Optional[str] = None):
         """boxes [n, k, 15, 6] -> (y [n, k, 4], logits [n, 15, k]), with the slot ids (and the lengths of a ragged call)
         already on the device (int32 [n], checked by the caller) and boxes checked: no host synchronisation"""
-        n, k = int(boxes.shape[0]), int(boxes.shape[1])
-        lib = _lib.load()
+        self._check_engine(engine, lengths)
         with torch.no_grad(), torch.cuda.device(self.device):
             boxes = boxes.contiguous().float()
-            packed = self.model._packed_weights(self.device)
-            stream = _stream_ptr(self.device)
-            ws = self._ws.get(stream, (n, k), self.device, (lib.opnet_stream_workspace_bytes, n, k, self.H1, self.H2))
-            y = torch.empty((n, k, 4), dtype=torch.float32, device=self.device)
-            logits = torch.empty((n, 15, k), dtype=torch.float32, device=self.device)
-            call_entry("opnet_stream_step_f32",
-                            [boxes.data_ptr(), slots.data_ptr(), self.state.data_ptr(), packed.data_ptr(), y.data_ptr(),
-                             logits.data_ptr(), ws.data_ptr(), ws.numel(), n, k, self.capacity, self.H1, self.H2, self._mlp,
-                             stream], lengths, 2)
+            if check_engine(engine, self.engine) == "persistent":
+                return self._step_persistent(slots, boxes)
+            self._prune_log()
+            before = self.state.index_select(0, slots.long()) if len(self._log) else None
+            out = self._step_chain(slots, boxes, lengths)
+            if before is not None:
+                self._log.record(slots, before, ("step", slots, boxes, lengths, *out))
+        return out
+
+    def _step_chain(self, slots: torch.Tensor, boxes: torch.Tensor, lengths: Optional[torch.Tensor], out=None):
+        """the launch-per-step engine (opnet_stream_step_f32); out: (y, logits) to fill instead of new tensors"""
+        n, k = int(boxes.shape[0]), int(boxes.shape[1])
+        lib = _lib.load()
+        packed = self.model._packed_weights(self.device)
+        stream = _stream_ptr(self.device)
+        ws = self._ws.get(stream, (n, k), self.device, (lib.opnet_stream_workspace_bytes, n, k, self.H1, self.H2))
+        direct = out is not None and out[0].is_contiguous() and out[1].is_contiguous()
+        y = out[0] if direct else torch.empty((n, k, 4), dtype=torch.float32, device=self.device)
+        logits = out[1] if direct else torch.empty((n, 15, k), dtype=torch.float32, device=self.device)
+        call_entry("opnet_stream_step_f32",
+                        [boxes.data_ptr(), slots.data_ptr(), self.state.data_ptr(), packed.data_ptr(), y.data_ptr(),
+                         logits.data_ptr(), ws.data_ptr(), ws.numel(), n, k, self.capacity, self.H1, self.H2, self._mlp,
+                         stream], lengths, 2)
+        if out is not None and not direct:
+            out[0].copy_(y)
+            out[1].copy_(logits)
+        return (y, logits) if out is None else out
+
+    def _step_persistent(self, slots: torch.Tensor, boxes: torch.Tensor):
+        """the same step as one persistent launch per piece (opnet_stream_step_x4_f32): pieces of at most
+        opnet_stream_x4_max_streams() streams, and of as many frames as one workspace holds (chunk invariance makes the cut
+        in time exact).  Every launch is watched by the model's monitor and logged for replay."""
+        n, k = int(boxes.shape[0]), int(boxes.shape[1])
+        lib = _lib.load()
+        H1, H2 = self.H1, self.H2
+        nmax = int(lib.opnet_stream_x4_max_streams())
+        kmax = k
+        while kmax > 1 and lib.opnet_stream_x4_workspace_bytes(min(n, nmax), kmax, H1, H2) == 0:
+            kmax = (kmax + 1) // 2
+        stream = _stream_ptr(self.device)
+        x4packed = self.model._x4_packed_weights(self.device, stream)
+        y = torch.empty((n, k, 4), dtype=torch.float32, device=self.device)
+        logits = torch.empty((n, 15, k), dtype=torch.float32, device=self.device)
+        self._prune_log()
+        for lo in range(0, n, nmax):
+            hi = min(n, lo + nmax)
+            m = hi - lo
+            sl = slots[lo:hi]
+            for t0 in range(0, k, kmax):
+                t1 = min(k, t0 + kmax)
+                kk = t1 - t0
+                whole = kk == k
+                bx = boxes[lo:hi] if whole else boxes[lo:hi, t0:t1].contiguous()
+                yy = y[lo:hi] if whole else torch.empty((m, kk, 4), dtype=torch.float32, device=self.device)
+                ll = logits[lo:hi] if whole else torch.empty((m, 15, kk), dtype=torch.float32, device=self.device)
+                ws = self._x4ws.get(stream, (m, kk), self.device, (lib.opnet_stream_x4_workspace_bytes, m, kk, H1, H2))
+                if self._gave_up:    # found by a watch of this very loop: the rest of the call runs on the chain, unlogged
+                    self._step_chain(sl, bx, None, (yy, ll))
+                    if not whole:
+                        y[lo:hi, t0:t1].copy_(yy)
+                        logits[lo:hi, :, t0:t1].copy_(ll)
+                    continue
+                entry = self._log.record(sl, self.state.index_select(0, sl.long()), ("step", sl, bx, None, yy, ll))
+                _lib.check(lib.opnet_stream_step_x4_f32(bx.data_ptr(), sl.data_ptr(), self.state.data_ptr(),
+                                                        x4packed.data_ptr(), yy.data_ptr(), ll.data_ptr(), ws.data_ptr(),
+                                                        ws.numel(), m, kk, self.capacity, H1, H2, stream),
+                           "opnet_stream_step_x4_f32")
+                entry.redo = lambda e=entry: self._heal(e)
+                self.model._monitor.watch(ws, lib.opnet_stream_x4_status_offset(m, kk, H1, H2), entry.redo,
+                                          "opnet_stream_step_x4")
+                if not whole:        # a piece in time -> its place in the caller's tensors, again after a replay of the piece
+                    def place(yv=y[lo:hi, t0:t1], lv=logits[lo:hi, :, t0:t1], yy=yy, ll=ll):
+                        yv.copy_(yy)
+                        lv.copy_(ll)
+                    place()
+                    self.log_followup(place)
         return y, logits
 
 
@@ -319,9 +588,11 @@ class LstmStackStreams(_StreamPool):
             self.state.index_copy_(0, torch.from_numpy(idx).to(self.device), rows)
 
     # -- frames -------------------------------------------------------------------------------
-    def _step_slots(self, slots: torch.Tensor, x: torch.Tensor, lengths: Optional[torch.Tensor] = None) -> torch.Tensor:
+    def _step_slots(self, slots: torch.Tensor, x: torch.Tensor, lengths: Optional[torch.Tensor] = None,
+                    engine: Optional[str] = None) -> torch.Tensor:
         """x [n, k, 15, 5] -> y [n, k, 4], with the slot ids (and the lengths of a ragged call) already on the device
-        (int32 [n], checked by the caller) and x checked: no host synchronisation"""
+        (int32 [n], checked by the caller) and x checked: no host synchronisation.  engine: None or "chain", the one there is"""
+        self._check_engine(engine, lengths)
         n, k = int(x.shape[0]), int(x.shape[1])
         S = self.slots_per_frame
         m = self.model

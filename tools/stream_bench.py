@@ -17,7 +17,11 @@ NonLinearLstm: one ragged call (host lengths, and an int32 device tensor), the s
 (one per k, each over the streams with that many frames), and a uniform call of k = 3 over all n.  device_us: HIP events
 around the window; wall_us: the window's wall time to the last call's completion, per call.
 
-    python tools/stream_bench.py [--model opnet] [--ns 1,32,256] [--ks 1,8,300] [--out result.json]
+--engine persistent times OPNetStreams' persistent engine (one persistent launch a call) in place of the launch
+chain; --engine both times the two in alternating windows (--rounds of them each) and reports every window, the minimum and
+the spread, per (n, k): stream_k{k} then holds {"chain": ..., "persistent": ..., "persistent_over_chain": ...}.
+
+    python tools/stream_bench.py [--model opnet] [--ns 1,32,256] [--ks 1,8,300] [--engine chain] [--out result.json]
     python tools/stream_bench.py --ragged [--ns 1,32,256] [--out result.json]
 """
 import argparse
@@ -61,6 +65,8 @@ def main():
     ap.add_argument("--ns", default="1,32,256")
     ap.add_argument("--ks", default="1,8,300")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--engine", default="chain", choices=["chain", "persistent", "both"], help="OPNetStreams engine (opnet)")
+    ap.add_argument("--rounds", type=int, default=3, help="--engine both: alternating windows per engine")
     ap.add_argument("--ragged", action="store_true", help="time ragged ticks (lengths 1, 2, 3) for all three models")
     args = ap.parse_args()
     if not torch.cuda.is_available():
@@ -100,8 +106,12 @@ def bench_opnet(args):
         for k in ks:
             x = boxes[:, :k].contiguous()
             calls = max(5, min(200, 1200 // k))
-            row[f"stream_k{k}"] = _time(lambda: streams.step(ids, x), calls)
+            if args.engine == "both":
+                row[f"stream_k{k}"] = _alternate(streams, ids, x, calls, args.rounds)
+                continue
+            row[f"stream_k{k}"] = _time(lambda: streams.step(ids, x, engine=args.engine), calls)
             row[f"stream_k{k}"]["device_us_per_frame"] = round(row[f"stream_k{k}"]["device_us"] / k, 2)
+            row["launches_gave_up"] = row.get("launches_gave_up", 0) + streams.verify_launches()
         # the same one-frame call straight through the C ABI with every buffer prepared: the kernels' cost without the
         # Python checks, the slot upload and the output allocations of OPNetStreams.step
         lib = _lib.load()
@@ -118,14 +128,30 @@ def bench_opnet(args):
                                                  y1.data_ptr(), lg1.data_ptr(), ws.data_ptr(), ws.numel(), n, 1, n, 256, 512, 0,
                                                  stream), "opnet_stream_step_f32")
         row["abi_k1"] = _time(abi_call, 200)
-        if 300 in ks:
+        if 300 in ks and args.engine != "both":
             row["k300_over_chain"] = round(row["stream_k300"]["device_us"] / row["whole_clip_chain"]["device_us"], 3)
-        if 1 in ks:
+        if 1 in ks and args.engine != "both":
             row["prefix_speedup_at_t300"] = round(row["whole_clip_default"]["device_us"] / row["stream_k1"]["device_us"], 1)
             row["prefix_speedup_vs_chain_at_t300"] = round(row["whole_clip_chain"]["device_us"] / row["stream_k1"]["device_us"], 1)
         res["rows"].append(row)
         print(json.dumps(row), file=sys.stderr, flush=True)
     return res
+
+
+def _alternate(streams, ids, x, calls, rounds):
+    """chain and persistent steps of the same call in alternating windows: every window's device time per call, the minimum
+    and the spread (max - min) / min per engine"""
+    windows = {"chain": [], "persistent": []}
+    gave_up = 0
+    for _ in range(rounds):
+        for engine in ("chain", "persistent"):
+            windows[engine].append(_time(lambda: streams.step(ids, x, engine=engine), calls)["device_us"])
+            gave_up += streams.verify_launches()
+    out = {"calls": calls, "launches_gave_up": gave_up}
+    for engine, w in windows.items():
+        out[engine] = {"device_us": min(w), "spread": round((max(w) - min(w)) / min(w), 3), "windows": w}
+    out["persistent_over_chain"] = round(out["persistent"]["device_us"] / out["chain"]["device_us"], 3)
+    return out
 
 
 STACK_CFG = {"baseline_lstm": {"videos_hidden_dim": 512},
