@@ -330,6 +330,23 @@ int opseq_stream_step_ragged_f32(const float *x, const int32_t *slots, const int
  * OPSEQ_STREAM_SKINNY_MAX_ROWS of them), 1 = the skinny kernel, 2 = the tiled GEMM + repack.  Same bits either way. */
 int opseq_stream_input_product_f32(const float *x, const float *packed, float *xg, void *workspace, size_t workspace_bytes,
                                    int n, int k, int L, int KX, int H, int route, void *stream);
+/* The uniform step as ONE persistent launch of the 4-clip form (opseq_xcd_forward_f32) that reads each named stream's state
+ * from the pool and writes it back: BaselineLstm (L = 1, KX <= 80) and NonLinearLstm (L = 2, hoisted input) at H = 512 on a
+ * whole MI355X (opseq_xcd_supported), n <= opseq_stream_x_max_streams(L) streams a call.  xpacked is the image of
+ * opseq_xcd_pack_weights_f32 and w_head predictions_layer.weight [4][H] (16-byte aligned), as opseq_xcd_forward_f32 takes
+ * them; every other argument, check and error code as opseq_stream_step_f32.  Five dependent launches whatever k (input pack
+ * or hoisted GEMM, prologue, the persistent launch, the output head, write-back).  Each frame has the arithmetic of
+ * opseq_xcd_forward_f32 over the same n clips: any chunking of a clip's frames into such calls gives the bits of that
+ * whole-clip forward (which differ from the launch chain's in the last places; both are fp32).  A state word with the bits
+ * 0xffffffff (a NaN) is read as the NaN 0x7fc00000.  A pool row may be advanced by either entry in any order.  The launch's
+ * status words lie at opseq_stream_x_status_offset(...) of the workspace; if it gave up (word 0 != 0) the named pool rows are
+ * left as they were before the call and y is NaN, so the caller can run the same call again through opseq_stream_step_f32. */
+int    opseq_stream_x_max_streams(int L);                                  /* = opseq_xcd_max_batch(L) */
+size_t opseq_stream_x_workspace_bytes(int n, int k, int L, int KX, int H); /* 0: not served (shape, n, >= 2 GiB) */
+size_t opseq_stream_x_status_offset(int n, int k, int L, int KX, int H);   /* (size_t)-1: not served */
+int    opseq_stream_step_x_f32(const float *x, const int32_t *slots, float *state, const float *xpacked,
+                               const float *w_head, float *y, void *workspace, size_t workspace_bytes,
+                               int n, int k, int capacity, int L, int KX, int H, void *stream);
 
 /* ---- the per-frame input encoder of the streams: detections -> input rows, on the device (DetectorStreams) ----------------
  * The detector's padded outputs of n streams x k frames - det_boxes [n][k][md][4] fp32 pixels (16-byte aligned),

@@ -162,6 +162,15 @@ def _declare(lib):
     lib.opnet_online_encode_ragged_f32.restype = c_int
     lib.opnet_online_encode_ragged_f32.argtypes = [fp, fp, fp, fp, fp, c_int, fp, fp, c_int, fp, c_int, c_int, c_int, c_int,
                                                    c_float, fp, c_void_p]
+    lib.opseq_stream_x_max_streams.restype = c_int
+    lib.opseq_stream_x_max_streams.argtypes = [c_int]
+    lib.opseq_stream_x_workspace_bytes.restype = c_size_t
+    lib.opseq_stream_x_workspace_bytes.argtypes = [c_int, c_int, c_int, c_int, c_int]
+    lib.opseq_stream_x_status_offset.restype = c_size_t
+    lib.opseq_stream_x_status_offset.argtypes = [c_int, c_int, c_int, c_int, c_int]
+    lib.opseq_stream_step_x_f32.restype = c_int
+    lib.opseq_stream_step_x_f32.argtypes = [fp, fp, fp, fp, fp, fp, c_void_p, c_size_t, c_int, c_int, c_int, c_int, c_int, c_int,
+                                            c_void_p]
     lib.opseq_stream_input_product_f32.restype = c_int
     lib.opseq_stream_input_product_f32.argtypes = [fp, fp, fp, c_void_p, c_size_t, c_int, c_int, c_int, c_int, c_int, c_int,
                                                    c_void_p]
@@ -349,6 +358,7 @@ EXPORTS = [
     "opseq_lstm_stack_forward_f32", "opseq_lstm_stack_forward_graph_f32", "opseq_graph_cache_clear",
     "opseq_stream_state_floats", "opseq_stream_workspace_bytes", "opseq_stream_step_f32", "opseq_stream_step_ragged_f32",
     "opseq_stream_input_product_f32",
+    "opseq_stream_x_max_streams", "opseq_stream_x_workspace_bytes", "opseq_stream_x_status_offset", "opseq_stream_step_x_f32",
     "opseq_xcd_supported", "opseq_xcd_enable", "opseq_xcd_max_batch", "opseq_xcd_packed_bytes", "opseq_xcd_workspace_bytes",
     "opseq_xcd_status_offset", "opseq_xcd_pack_weights_f32", "opseq_xcd_forward_f32", "opseq_lstm_stack_train_status_offset", "opseq_xcd_set_trace",
     "opseq_xcdt_supported", "opseq_xcdt_enable", "opseq_xcdt_max_batch", "opseq_xcdt_packed_bytes", "opseq_xcdt_workspace_bytes",

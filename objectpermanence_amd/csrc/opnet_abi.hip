@@ -17,6 +17,7 @@
 #include "opnet_stream_kernels.hip"
 #include "opnet_stream_x4_kernels.hip"
 #include "seq_stream_kernels.hip"
+#include "seq_stream_x_kernels.hip"
 #include "online_encode_kernels.hip"
 
 #include <stdarg.h>

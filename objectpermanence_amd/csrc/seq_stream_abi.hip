@@ -154,3 +154,101 @@ extern "C" int opseq_stream_input_product_f32(const float *x, const float *packe
     HIP_TRY(hipGetLastError());
     return OPNET_OK;
 }
+
+// ------------------------------------------------------------------------------------------------
+// the same uniform step as ONE persistent launch of the 4-clip form (kernels: seq_stream_x_kernels.hip, seq_xcd_kernels.hip)
+// ------------------------------------------------------------------------------------------------
+// opseq_xcd_forward_f32's workspace (seqx_ws_layout, unchanged) with the cell-state staging buffers behind it
+struct SeqXStreamLayout { SeqXWs W; size_t cs[2], total; };      // bytes
+static SeqXStreamLayout seqx_stream_layout(int n, int k, int L, int KX, int H)
+{
+    SeqXStreamLayout S;
+    S.W = seqx_ws_layout(n, k, L, KX, H);
+    const size_t NGT = (n + 3) / 4;
+    size_t o = S.W.total;
+    for (int l = 0; l < 2; ++l) {
+        S.cs[l] = o; if (l < L) o += NGT * SX_H * 4 * sizeof(float);
+    }
+    S.total = align_up(o, 4096);
+    return S;
+}
+static int check_seqx_stream(int n, int k, int L, int KX, int H)
+{
+    if (int rc = check_seqx(n, k, L, KX, H)) return rc;
+    if (L == 2 && seqx_nxq0(KX, H) != 0)
+        return fail(OPNET_ESHAPE, "a persistent stream step is built for BaselineLstm (L=1, KX<=80) and NonLinearLstm (L=2, hoisted "
+                                  "input); got L=%d KX=%d H=%d (transformer_lstm is not streamed)", L, KX, H);
+    if (seqx_stream_layout(n, k, L, KX, H).total >= ((size_t)1 << 31))
+        return fail(OPNET_ESHAPE, "n=%d x k=%d: the workspace exceeds the 2 GiB one buffer descriptor addresses", n, k);
+    return OPNET_OK;
+}
+
+extern "C" int opseq_stream_x_max_streams(int L) { return opseq_xcd_max_batch(L); }
+
+extern "C" size_t opseq_stream_x_workspace_bytes(int n, int k, int L, int KX, int H)
+{
+    if (check_seqx_stream(n, k, L, KX, H)) return 0;
+    return seqx_stream_layout(n, k, L, KX, H).total;
+}
+
+extern "C" size_t opseq_stream_x_status_offset(int n, int k, int L, int KX, int H)
+{
+    if (check_seqx_stream(n, k, L, KX, H)) return (size_t)-1;
+    return seqx_stream_layout(n, k, L, KX, H).W.status;
+}
+
+// [input pack | hoisted GEMM] -> prologue -> the persistent launch -> out_head -> write-back: five dependent launches on
+// `stream` whatever k, no host synchronisation
+extern "C" int opseq_stream_step_x_f32(const float *x, const int32_t *slots, float *state, const float *xpacked,
+                                       const float *w_head, float *y, void *workspace, size_t workspace_bytes, int n, int k,
+                                       int capacity, int L, int KX, int H, void *stream)
+{
+    if (int rc = check_seqx_stream(n, k, L, KX, H)) return rc;
+    if (capacity <= 0) return fail(OPNET_ESHAPE, "capacity=%d must be positive", capacity);
+    if (!x || !slots || !state || !xpacked || !w_head || !y || !workspace) return fail(OPNET_EINVAL, "null pointer");
+    const int nxq0 = seqx_nxq0(KX, H);
+    if (!aligned16(state) || !aligned16(xpacked) || !aligned16(w_head) || !aligned16(y) || !aligned16(workspace) ||
+        (((uintptr_t)slots) & 3u) || (((uintptr_t)x) & (nxq0 == 0 ? 15u : 3u)))
+        return fail(OPNET_EINVAL, "state/xpacked/w_head/y/workspace must be 16-byte aligned, slots 4-byte and x %d-byte",
+                    nxq0 == 0 ? 16 : 4);
+    const SeqXStreamLayout S = seqx_stream_layout(n, k, L, KX, H);
+    if (workspace_bytes < S.total) return fail(OPNET_EWORKSPACE, "workspace %zu B < %zu B", workspace_bytes, S.total);
+    int dev = 0;
+    if (int rc = persistent_device(&dev)) return rc;
+    const SeqXHostPacked PK = seqx_host_packed(L, KX, H);
+    hipStream_t st = (hipStream_t)stream;
+    char *w = (char *)workspace;
+    const int RB = (n + 31) / 32;
+    SeqStreamXArgs s;
+    memset(&s, 0, sizeof(s));
+    SeqXArgs &a = s.a;
+    a.B = n; a.T = k; a.L = L; a.NGT = (n + 3) / 4; a.RB = RB; a.KXQ = nxq0;
+    a.pk = xpacked + PK.regs;
+    a.whead = w_head;
+    a.ws = w;
+    a.xp_off = (unsigned)S.W.xp; a.g_off = (unsigned)S.W.gemm;
+    for (int l = 0; l < 2; ++l) {
+        a.hl_off[l] = (unsigned)S.W.hl[l]; a.hc_off[l] = (unsigned)S.W.hc[l]; a.cs_off[l] = (unsigned)S.cs[l];
+    }
+    a.status = (unsigned *)(w + S.W.status);
+    a.ystage = (float4 *)y;
+    a.force_safe = env_int("OPNET_XCD_SAFE", 0);
+    s.slots = slots;
+    s.state = state;
+    s.capacity = capacity;
+    if (nxq0 == 0)      // G [n*k][4H] = x [n*k][KX] . W_ih0^T; the cell reads it where it lies
+        launch_conv_tiled(row_gemm_args(x, xpacked + PK.wih0g, nullptr, nullptr, (float *)(w + S.W.gemm), (long)n * k, 4 * H, KX, 0),
+                          (long)n * k, st);
+    else
+        rows_to_packed<<<1024, 256, 0, st>>>(x, (float4 *)(w + S.W.xp), n, k, RB, KX, 4 * nxq0, nullptr, 0);
+    seq_stream_x_prologue<<<512, 256, 0, st>>>(s);
+    if (int rc = persistent_launch(dev, st, PROF_SEQX, [&] {
+            if (L == 1) seqx_forward<20, 1, false, true><<<XCD_COUNT * XCD_CUS, 256, 0, st>>>(a);
+            else seqx_forward<0, 2, false, true><<<XCD_COUNT * XCD_CUS, 256, 0, st>>>(a);
+        }))
+        return rc;
+    seqx_out_head<<<dim3(k, a.NGT), 64, 0, st>>>(a);
+    seq_stream_x_writeback<<<ew_blocks((long)a.NGT * L * SSX_Q * 4, 1024), 256, 0, st>>>(s);
+    HIP_TRY(hipGetLastError());
+    return OPNET_OK;
+}

@@ -90,6 +90,8 @@ struct SeqXArgs {
     float *call[2];            // [T + 1][RB][512][32]
     float4 *gsave[2];          // [T][RB][512][32]
     unsigned long long *trace; // tools: [8 XCDs][4 waves][phases][8] s_memtime stamps of CU 0 of every XCD (null = off)
+    unsigned cs_off[2];        // seqx_forward<.., false, true> (stream steps) only: per layer the cell states in and out,
+                               // [NGT groups][512 units][4 clips] float = the sC entries of every (group, CU), CU by CU
 };
 
 typedef float sx_f32x4 __attribute__((ext_vector_type(4)));
@@ -217,10 +219,43 @@ __device__ __forceinline__ void sx_products(sx_f32x4 (&c)[8], const AT &A, const
     if (MIDQ >= NQ) mid();
 }
 
+// seqx_forward<.., STATE = true>: behind the phase loop the cell wave (on = wave 0) hands its c back to the staging buffer, each
+// lane the entries sC[g][lane] it alone has written (no barrier needed): group g of the CU at byte off + g * step of the workspace.
+// The loop is left by its break and, when the launch gives up, by its returns; this is a destructor so that it runs on every way
+// out and the loop's own control flow is what it is without STATE.  It looks at the abort word itself: sAbort is raised in front
+// of a phase's last barrier, and only a workgroup that has seen it raised leaves early.  If ANOTHER workgroup gave up, what lands
+// here is never used: the write-back looks at status[0] before it touches a pool row.  STATE = false: nothing, nothing is kept.
+template <bool STATE> struct SxHandBackC {
+    __device__ __forceinline__ SxHandBackC(__amdgpu_buffer_rsrc_t, unsigned, unsigned, unsigned, int, bool, const float *, int *) {}
+};
+template <> struct SxHandBackC<true> {
+    const __amdgpu_buffer_rsrc_t rws;
+    const unsigned off, step, soff;
+    const int ng;
+    const bool on;
+    const float *const sc;           // &sC[0][lane]
+    int *const abort_word;
+    __device__ __forceinline__ SxHandBackC(__amdgpu_buffer_rsrc_t rws_, unsigned off_, unsigned step_, unsigned soff_, int ng_, bool on_,
+                                           const float *sc_, int *abort_)
+        : rws(rws_), off(off_), step(step_), soff(soff_), ng(ng_), on(on_), sc(sc_), abort_word(abort_) {}
+    __device__ __forceinline__ ~SxHandBackC()
+    {
+        if (on && !XCD_LDS_LD(*abort_word))
+            for (int g = 0; g < ng; ++g) xcd_st1(rws, off + g * step, soff, sc[g * 64]);
+    }
+};
+
 // NXT0: k-quads of layer 0's direct input (0 = hoisted: the cell adds G); L: layers; TRAIN: keep the backward's histories
-template <int NXT0, int L, bool TRAIN>
+// STATE (inference only; opseq_stream_step_x_f32): the launch continues streams instead of starting clips.  h of the step before
+// the first is whatever the launch in front put into slot 0 of the exchange buffers (seq_stream_x_prologue) - the phase loop
+// gathers "step -1" from there as it always has -; c is loaded from cs_off[l] in place of the zero fill and stored back once
+// behind the phase loop.  Nothing between differs and nothing new is fenced: both directions cross a kernel boundary (the
+// prologue's stores -> this launch, this launch's stores -> seq_stream_x_writeback), as seqx_init's fill and seqx_out_head's
+// reads of the top layer's history do.
+template <int NXT0, int L, bool TRAIN, bool STATE = false>
 __global__ void __launch_bounds__(256) seqx_forward(const SeqXArgs a)
 {
+    static_assert(!(TRAIN && STATE), "the training forward starts every clip from the zero state");
     constexpr int NXW0 = sx_xw(NXT0), NXW1 = sx_xw(SX_XT1);
     constexpr int NXWMAX = L == 2 ? NXW1 : (NXW0 > 0 ? NXW0 : 1);
     __shared__ __attribute__((aligned(1024))) float4 sH[4][128];         // wave-private: the wave's quarter of h[t-1]
@@ -249,7 +284,18 @@ __global__ void __launch_bounds__(256) seqx_forward(const SeqXArgs a)
             if (loc == 0 && c == 0) atomicAdd(a.status + 3, 1u);
         }
     }
-    for (int i = tid; i < SX_NGMAX * 64; i += 256) (&sC[0][0])[i] = 0.f;
+    if (STATE) {
+        // this CU's (group gi * NPAIR + pr, units 16 c .. 16 c + 15) entries of its layer: sC lane = 4 b + j = 4 (unit - 16 c) + clip
+        // (through a buffer descriptor, as the loop's accesses: no flat pointer to the workspace is kept for it)
+        const __amdgpu_buffer_rsrc_t rcs = __builtin_amdgcn_make_buffer_rsrc((void *)a.ws, 0, 0x7fffffff, 0x00020000);
+        const unsigned cs_mine = (L == 2 && l == 1) ? a.cs_off[1] : a.cs_off[0];
+        for (int i = tid; i < SX_NGMAX * 64; i += 256)
+            (&sC[0][0])[i] = (i >> 6) < ng ? __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(
+                                                 rcs, (unsigned)((((i >> 6) * NPAIR + pr) * 32 + c) * 64 + (i & 63)) * 4, cs_mine, 0))
+                                           : 0.f;
+    } else {
+        for (int i = tid; i < SX_NGMAX * 64; i += 256) (&sC[0][0])[i] = 0.f;
+    }
     if (a.debug & 0x40000000) sPad[tid * 16] = make_float4(0.f, 0.f, 0.f, 0.f);     // (keeps the padding allocated)
     // this XCD's layer: its buffers and histories (selected here once - indexing the kernarg arrays by l costs scratch)
     const unsigned hl_mine = l == 0 ? a.hl_off[0] : a.hl_off[1];
@@ -299,6 +345,10 @@ __global__ void __launch_bounds__(256) seqx_forward(const SeqXArgs a)
     const bool top = l == L - 1;
     const int nph = T * ng;
     constexpr int NLD = (NXWMAX + 15) / 16;                      // 1-KB pieces (16 k-quads x 4 clips) an x wave loads per phase
+
+    // STATE: c goes back to cs[l], entry ((g * NPAIR + pr) * 32 + c) * 64 + lane, when the kernel is left (SxHandBackC)
+    const SxHandBackC<STATE> hand_back_c(rws, (unsigned)((pr * 32 + c) * 64 + lane) * 4, NPAIR * 32 * 64 * 4,
+                                         (L == 2 && l == 1) ? a.cs_off[1] : a.cs_off[0], ng, w == 0, &sC[0][lane], &sAbort);
 
     int gi = 0, t = 0;              // the phase this iteration computes the products of
     int gp = 0, tp = 0;             // the previous phase (whose cell wave 0 computes now)

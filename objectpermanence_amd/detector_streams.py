@@ -26,8 +26,9 @@ list of per-stream frame arrays [k_i, H, W, 3] for step.  Frames past a stream's
 without detections for the encoder (nothing is learned from them, they encode as zeros) and never reach the pool's state.
 
 A backlog of many frames can run as one persistent launch instead of the launch chain: `DetectorStreams(..., engine=)` sets the
-OPNet pool's default engine, `step(..., engine=)` / `step_detections(..., engine=)` choose per call (streaming.OPNetStreams;
-uniform calls only, refused for the stacked reasoners); `verify_launches()` at a sync point, as on the pool.
+OPNet pool's default engine (the constructor's `engine=` is served for OPNet only), `step(..., engine=)` /
+`step_detections(..., engine=)` choose per call for every pool that has the engine (streaming.OPNetStreams and
+streaming.LstmStackStreams; uniform calls only); `verify_launches()` at a sync point, as on the pool.
 
 `encode_detections_numpy` is the readable statement the kernel is held to bit for bit, as encode_boxes is to the native
 clip encoder.  step_detections and encode do not synchronise the host: slot ids go up through fresh pinned buffers, and
@@ -181,8 +182,8 @@ class DetectorStreams:
             pool, tracks = OPNetStreams(model, capacity, engine=engine), 6
         elif isinstance(model, (BaselineLstm, NonLinearLstm)):
             if check_engine(engine) != "chain":
-                raise ValueError(f"engine={engine!r} is served for OPNet only: {type(model).__name__} streams "
-                                 "(LstmStackStreams) run on the launch chain")
+                raise ValueError(f"engine={engine!r} as a pool default is served for OPNet only: {type(model).__name__} "
+                                 "streams (LstmStackStreams) take engine='persistent' per call, step(..., engine=)")
             pool, tracks = LstmStackStreams(model, capacity), 5
         else:
             raise TypeError(f"DetectorStreams serves OPNet, OPNetLstmMlp, BaselineLstm and NonLinearLstm, not "
@@ -289,10 +290,8 @@ class DetectorStreams:
 
     # -- frames -------------------------------------------------------------------------------
     def verify_launches(self) -> int:
-        """as OPNetStreams.verify_launches: wait for the model's persistent launches, heal a step that gave up"""
-        if isinstance(self.pool, OPNetStreams):
-            return self.pool.verify_launches()
-        return 0
+        """as the pool's verify_launches: wait for the model's persistent launches, heal a step that gave up"""
+        return self.pool.verify_launches()
 
     def _check_engine(self, engine, lengths) -> None:
         """before anything is encoded: an engine the pool refuses must not leave the slot tables half updated"""
@@ -314,14 +313,13 @@ class DetectorStreams:
             pixels()
             # y of an unverified persistent step (and of every step behind it) may still be rewritten by the pool's replay:
             # the pixel boxes are then derived again, into the px the caller holds
-            if isinstance(self.pool, OPNetStreams):
-                self.pool.log_followup(pixels)
+            self.pool.log_followup(pixels)
         return StreamResult(px, y, logits, x, detections, lengths)
 
     def step_detections(self, ids: Sequence[int], boxes: torch.Tensor, scores: torch.Tensor, labels: torch.Tensor,
                         n_det: torch.Tensor, lengths=None, engine: Optional[str] = None) -> StreamResult:
         """encode k frames of detections of your own detector (as `encode`) and advance the streams by them (stream i by
-        its first lengths[i] when lengths are given).  engine: "chain" or "persistent" (OPNet pools, uniform calls) for this
+        its first lengths[i] when lengths are given).  engine: "chain" or "persistent" (uniform calls) for this
         call, None = the pool's default.  No host sync."""
         self._check_engine(engine, lengths)
         slots, lens, x = self._encode(ids, boxes, scores, labels, n_det, lengths)

@@ -631,15 +631,21 @@ class _LstmStackRunner:
             return False
         return T is None or int(lib.opseq_xcd_workspace_bytes(B, T, self.L, self.KX, self.H)) > 0
 
+    def _x_packed_weights(self, ws_list, dev: torch.device, stream: int) -> torch.Tensor:
+        """the 4-clip persistent kernel's weight image (opseq_xcd_pack_weights_f32) of ws_list for launches on `stream`; shared
+        by _run_xcd and the persistent engine of streaming.LstmStackStreams"""
+        lib = _lib.load()
+        return self._xpacked.get(stream, ws_list, dev, (lib.opseq_xcd_packed_bytes, self.L, self.KX, self.H),
+                                 lambda buf, n: _lib.check(lib.opseq_xcd_pack_weights_f32(
+                                     *self._layer_ptrs(ws_list), buf.data_ptr(), n, self.L, self.KX, self.H, stream),
+                                     "opseq_xcd_pack_weights_f32"))
+
     def _run_xcd(self, x: torch.Tensor, ws_list, head: "LinearWeight") -> torch.Tensor:
         lib = _lib.load()
         dev = x.device
         B, T = int(x.shape[0]), int(x.shape[1])
         stream = _stream_ptr(dev)
-        packed = self._xpacked.get(stream, ws_list, dev, (lib.opseq_xcd_packed_bytes, self.L, self.KX, self.H),
-                                   lambda buf, n: _lib.check(lib.opseq_xcd_pack_weights_f32(
-                                       *self._layer_ptrs(ws_list), buf.data_ptr(), n, self.L, self.KX, self.H, stream),
-                                       "opseq_xcd_pack_weights_f32"))
+        packed = self._x_packed_weights(ws_list, dev, stream)
         ws = self._xws.get(stream, (B, T), dev, (lib.opseq_xcd_workspace_bytes, B, T, self.L, self.KX, self.H))
         y = torch.empty((B, T, 4), dtype=torch.float32, device=dev)
         _lib.check(lib.opseq_xcd_forward_f32(x.data_ptr(), packed.data_ptr(), head.weight.data_ptr(), y.data_ptr(), ws.data_ptr(),

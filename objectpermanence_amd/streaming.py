@@ -36,6 +36,11 @@ chunk-invariant on its own; the two round differently in the last places, which 
 choice and never a function of k.  Persistent steps are watched by the model's LaunchMonitor: call `verify_launches()` at a
 sync point before trusting outputs on the host, as after `model(boxes)`.
 
+`LstmStackStreams(model, capacity, engine="persistent")` / `step(ids, x, engine="persistent")` is the same choice for the
+stacked reasoners (opseq_stream_step_x_f32: the 4-clip persistent stacked LSTM, seqx_forward, with the state handed in and
+out; H = 512 shapes that opseq_xcd_supported accepts, on a whole MI355X, uniform calls only), with the same rules: no
+automatic choice, a checked precondition and not a fallback, watched by the runner's LaunchMonitor and healed on the chain.
+
 TransformerLstm is not streamed: its encoder attends over the whole sequence, so a frame's output depends on later frames.
 """
 from __future__ import annotations
@@ -221,6 +226,10 @@ class _StreamPool:
         self.slots = slots
         self.capacity = slots.capacity
         self._ws = Workspaces(8)
+        self._gave_up = False
+        self._log = StreamReplayLog(self._restore_rows, self._rerun)
+        self.healed_calls = 0            # calls run again on the chain after a persistent step gave up
+        self.engine = "chain"
 
     def _alloc_state(self, row: int, what: str) -> None:
         if row == 0:
@@ -237,7 +246,11 @@ class _StreamPool:
         """`count` new streams with a zero state (the reference's h0 = c0 = 0); returns their slot ids"""
         ids = self.slots.open(count)
         with torch.cuda.device(self.device):
-            self.state.index_fill_(0, torch.from_numpy(ids).to(self.device), 0.0)
+            dst = torch.from_numpy(ids).to(self.device)
+            self.state.index_fill_(0, dst, 0.0)
+            if len(self._log):       # a replay must zero the rows again
+                self._log.record(dst, torch.zeros((len(ids), self._row), dtype=torch.float32, device=self.device),
+                                 ("rows", dst, None))
         return [int(i) for i in ids]
 
     def close(self, ids: Sequence[int]) -> None:
@@ -248,8 +261,8 @@ class _StreamPool:
         """advance the streams `ids` by k frames: x [n, k, S, F] (row i belongs to ids[i]) -> the outputs of those frames
         (OPNetStreams: boxes [n, k, 15, 6] -> (y [n, k, 4], logits [n, 15, k]); LstmStackStreams: x [n, k, 15, 5] ->
         y [n, k, 4]).  lengths ([n] ints in 0..k, on the host or an int32 device tensor): stream i advances by its first
-        lengths[i] frames only; the outputs are +0.0 on the others.  engine (OPNetStreams): "chain" or "persistent" for
-        this call, None = the pool's default."""
+        lengths[i] frames only; the outputs are +0.0 on the others.  engine: "chain" or "persistent" for this call,
+        None = the pool's default."""
         self._check_engine(engine, lengths)
         name = self._frames
         if not isinstance(x, torch.Tensor) or not x.is_cuda:
@@ -264,11 +277,85 @@ class _StreamPool:
         slots, lens = self._device_ids(idx, lengths, int(x.shape[1]))
         return self._step_slots(slots, x, lens, engine=engine)
 
+    # -- engines ------------------------------------------------------------------------------
+    def _launch_monitor(self):
+        """the LaunchMonitor that watches the model's persistent launches"""
+        return self.model._monitor
+
+    def _check_persistent(self) -> None:
+        """the preconditions of the pool's persistent engine, or an exception (the subclass's)"""
+        raise NotImplementedError
+
+    def _check_not_given_up(self) -> None:
+        if self._gave_up:
+            raise RuntimeError("a persistent step of this pool gave up earlier and was healed on the launch chain; the pool "
+                               "stays on engine='chain'")
+
     def _check_engine(self, engine, lengths) -> None:
-        """a pool with one engine takes no `engine` (OPNetStreams overrides this)"""
-        if engine is not None and check_engine(engine) != "chain":
-            raise ValueError(f"{type(self).__name__} has one engine, the launch chain: engine={engine!r} is served by "
-                             "OPNetStreams only")
+        if check_engine(engine, self.engine) != "persistent":
+            return
+        self._check_persistent()
+        if lengths is not None:
+            raise ValueError("engine='persistent' takes uniform calls only: ragged persistent steps are not built "
+                             "(pass lengths with engine='chain')")
+
+    def verify_launches(self) -> int:
+        """wait for the persistent steps (and forwards) of the model issued so far; a step that gave up is healed: the pool
+        is rewound to the state before it, that call and every later one run again on the launch chain into the tensors they
+        returned, and the pool stays on the chain.  Returns the number of launches that gave up.  Call it at the sync point
+        you already have, before anything reads a persistent step's outputs on the host."""
+        n = verify_launches(self.model)
+        self._prune_log()
+        return n
+
+    # -- the replay log (StreamReplayLog) -----------------------------------------------------------
+    def _prune_log(self) -> None:
+        if len(self._log):
+            mon = self._launch_monitor()
+            mon.reap()
+            self._log.prune(lambda e: mon.watching(e.redo))
+
+    def _log_write(self, dst: torch.Tensor, rows: torch.Tensor) -> None:
+        """a set_state while the log is kept: a replay has to repeat it"""
+        self._prune_log()
+        if len(self._log):
+            self._log.record(dst, self.state.index_select(0, dst), ("rows", dst, rows.clone()))
+
+    def log_followup(self, fn: Callable[[], None]) -> None:
+        """device work a caller derived from the outputs of the step it has just made (DetectorStreams: the pixel boxes of
+        y): while the log is kept it is recorded behind that step, so that a replay which rewrites the step's outputs runs
+        `fn()` again - into the same tensors, which is `fn`'s business.  Names no pool rows."""
+        if len(self._log):
+            self._log.record(self.state.new_empty(0, dtype=torch.int64), self.state[:0], ("call", fn))
+
+    def _restore_rows(self, slots: torch.Tensor, before: torch.Tensor) -> None:
+        self.state.index_copy_(0, slots.long(), before)
+
+    def _rerun(self, payload) -> None:
+        if payload[0] == "call":         # work derived from a step's outputs (log_followup)
+            payload[1]()
+            return
+        if payload[0] == "rows":
+            _, dst, rows = payload
+            if rows is None:
+                self.state.index_fill_(0, dst, 0.0)
+            else:
+                self.state.index_copy_(0, dst, rows)
+            return
+        _, slots, x, lengths, *out = payload
+        self._step_chain(slots, x, lengths, tuple(out))
+        self.healed_calls += 1
+
+    def _heal(self, entry: ReplayEntry) -> None:
+        """the monitor's redo of a persistent step that gave up"""
+        if entry.healed:
+            return               # run again already, behind an earlier step that gave up
+        with torch.no_grad(), torch.cuda.device(self.device):
+            self.engine, self._gave_up = "chain", True     # for good: a later engine="persistent" is refused
+            # the later calls of the log may still be running, on other streams too: the rows are put back behind all of them
+            torch.cuda.synchronize(self.device)
+            self._log.replay(entry)
+            self._log.clear()
 
     def _device_ids(self, idx: np.ndarray, lengths, k: int):
         """(slots, lengths) on the device for a call of k frames: the uniform call (lengths None) uploads the slot ids as
@@ -311,10 +398,6 @@ class OPNetStreams(_StreamPool):
         self._alloc_state(_lib.load().opnet_stream_state_floats(self.H1, self.H2), "opnet_stream_state_floats")
         self._x4ws = Workspaces(8)
         self._x4_ok: Optional[bool] = None
-        self._gave_up = False
-        self._log = StreamReplayLog(self._restore_rows, self._rerun)
-        self.healed_calls = 0            # calls run again on the chain after a persistent step gave up
-        self.engine = "chain"
         if engine == "persistent":
             self._check_persistent()
             self.engine = engine
@@ -327,32 +410,13 @@ class OPNetStreams(_StreamPool):
         """the preconditions of the persistent engine, or an exception"""
         if self._mlp:
             raise TypeError(self._NO_MLP)
-        if self._gave_up:
-            raise RuntimeError("a persistent step of this pool gave up earlier and was healed on the launch chain; the pool "
-                               "stays on engine='chain'")
+        self._check_not_given_up()
         if self._x4_ok is None:
             with torch.cuda.device(self.device):
                 self._x4_ok = bool(_lib.load().opnet_xcd_supported(self.H1, self.H2))
         if not self._x4_ok:
             raise ValueError(f"engine='persistent' needs the reference hidden sizes (256, 512) on a whole MI355X (8 XCDs x 32 "
                              f"CUs visible); this pool has H1={self.H1}, H2={self.H2} on {self.device}: use engine='chain'")
-
-    def _check_engine(self, engine, lengths) -> None:
-        if check_engine(engine, self.engine) != "persistent":
-            return
-        self._check_persistent()
-        if lengths is not None:
-            raise ValueError("engine='persistent' takes uniform calls only: ragged persistent steps are not built "
-                             "(pass lengths with engine='chain')")
-
-    def verify_launches(self) -> int:
-        """wait for the persistent steps (and forwards) of the model issued so far; a step that gave up is healed: the pool
-        is rewound to the state before it, that call and every later one run again on the launch chain into the tensors they
-        returned, and the pool stays on the chain.  Returns the number of launches that gave up.  Call it at the sync point
-        you already have, before anything reads a persistent step's outputs on the host."""
-        n = verify_launches(self.model)
-        self._prune_log()
-        return n
 
     # -- state --------------------------------------------------------------------------------
     def get_state(self, ids: Sequence[int]):
@@ -396,64 +460,6 @@ class OPNetStreams(_StreamPool):
                 rows = torch.cat(cols, dim=1)
                 self._log_write(dst, rows)
                 self.state.index_copy_(0, dst, rows)
-
-    def open(self, count: int = 1) -> List[int]:
-        ids = super().open(count)
-        if len(self._log):       # a replay must zero the rows again
-            with torch.cuda.device(self.device):
-                dst = torch.tensor(ids, dtype=torch.int64).to(self.device)
-                self._log.record(dst, torch.zeros((len(ids), self._row), dtype=torch.float32, device=self.device),
-                                 ("rows", dst, None))
-        return ids
-
-    # -- the replay log (StreamReplayLog) -----------------------------------------------------------
-    def _prune_log(self) -> None:
-        if len(self._log):
-            mon = self.model._monitor
-            mon.reap()
-            self._log.prune(lambda e: mon.watching(e.redo))
-
-    def _log_write(self, dst: torch.Tensor, rows: torch.Tensor) -> None:
-        """a set_state while the log is kept: a replay has to repeat it"""
-        self._prune_log()
-        if len(self._log):
-            self._log.record(dst, self.state.index_select(0, dst), ("rows", dst, rows.clone()))
-
-    def log_followup(self, fn: Callable[[], None]) -> None:
-        """device work a caller derived from the outputs of the step it has just made (DetectorStreams: the pixel boxes of
-        y): while the log is kept it is recorded behind that step, so that a replay which rewrites the step's outputs runs
-        `fn()` again - into the same tensors, which is `fn`'s business.  Names no pool rows."""
-        if len(self._log):
-            self._log.record(self.state.new_empty(0, dtype=torch.int64), self.state[:0], ("call", fn))
-
-    def _restore_rows(self, slots: torch.Tensor, before: torch.Tensor) -> None:
-        self.state.index_copy_(0, slots.long(), before)
-
-    def _rerun(self, payload) -> None:
-        if payload[0] == "call":         # work derived from a step's outputs (log_followup)
-            payload[1]()
-            return
-        if payload[0] == "rows":
-            _, dst, rows = payload
-            if rows is None:
-                self.state.index_fill_(0, dst, 0.0)
-            else:
-                self.state.index_copy_(0, dst, rows)
-            return
-        _, slots, boxes, lengths, y, logits = payload
-        self._step_chain(slots, boxes, lengths, (y, logits))
-        self.healed_calls += 1
-
-    def _heal(self, entry: ReplayEntry) -> None:
-        """the monitor's redo of a persistent step that gave up"""
-        if entry.healed:
-            return               # run again already, behind an earlier step that gave up
-        with torch.no_grad(), torch.cuda.device(self.device):
-            self.engine, self._gave_up = "chain", True     # for good: a later engine="persistent" is refused
-            # the later calls of the log may still be running, on other streams too: the rows are put back behind all of them
-            torch.cuda.synchronize(self.device)
-            self._log.replay(entry)
-            self._log.clear()
 
     # -- frames -------------------------------------------------------------------------------
     def _step_slots(self, slots: torch.Tensor, boxes: torch.Tensor, lengths: Optional[torch.Tensor] = None,
@@ -544,12 +550,13 @@ class OPNetStreams(_StreamPool):
 
 class LstmStackStreams(_StreamPool):
     """A pool of `capacity` BaselineLstm (or NonLinearLstm) streams on the model's ROCm device.  Calls are enqueued on the
-    current torch stream and are inference only (no autograd graph).  The model's own packed weight image (the launch
-    chain's, _LstmStackRunner._packed_weights) is used, so an in-place parameter update takes effect on the next call.
-    A stream's state row is [h_0 | c_0 | h_1 | c_1 ...] over the model's L layers."""
+    current torch stream and are inference only (no autograd graph).  The model's own packed weight images (the launch
+    chain's, _LstmStackRunner._packed_weights, and the persistent kernel's, _x_packed_weights) are used, so an in-place
+    parameter update takes effect on the next call.  A stream's state row is [h_0 | c_0 | h_1 | c_1 ...] over the model's L
+    layers.  engine: the pool's default, "chain" or "persistent" (module docstring); `step(..., engine=)` chooses per call."""
     _frames, _frames_are = "x", "x is"
 
-    def __init__(self, model, capacity: int = 1024):
+    def __init__(self, model, capacity: int = 1024, engine: str = "chain"):
         if isinstance(model, NonLinearLstm):
             self._embed = True
         elif isinstance(model, BaselineLstm):
@@ -558,12 +565,42 @@ class LstmStackStreams(_StreamPool):
             raise TypeError(f"LstmStackStreams serves BaselineLstm and NonLinearLstm, not {type(model).__name__} (OPNet and "
                             "OPNetLstmMlp are streamed by OPNetStreams; transformer_lstm is not streamed: its encoder "
                             "attends over the whole sequence, so it is not causal)")
-        super().__init__(model, capacity)
+        engine = check_engine(engine)
         r = model._runner
         self.L, self.KX, self.H = r.L, r.KX, r.H
+        if engine == "persistent":
+            self._check_persistent_shape()
+        super().__init__(model, capacity)
         self.slots_per_frame, self.features = model.max_objects_in_frame, model.bb_in_dim
         self._frame_shape = (self.slots_per_frame, self.features)
         self._alloc_state(_lib.load().opseq_stream_state_floats(self.L, self.H), "opseq_stream_state_floats")
+        self._xws = Workspaces(8)
+        self._x_ok: Optional[bool] = None
+        if engine == "persistent":
+            self._check_persistent()
+            self.engine = engine
+
+    # -- engines ------------------------------------------------------------------------------
+    def _launch_monitor(self):
+        return self.model._runner._monitor
+
+    def _check_persistent_shape(self) -> None:
+        """the persistent kernel's shapes (a host-side question: asked before the pool exists)"""
+        if _lib.load().opseq_stream_x_workspace_bytes(1, 1, self.L, self.KX, self.H) == 0:
+            raise ValueError(f"engine='persistent' needs the reference shapes of the stacked reasoners (H = 512; BaselineLstm's "
+                             f"one layer with KX <= 80, NonLinearLstm's two with a hoisted input); this model has L={self.L}, "
+                             f"KX={self.KX}, H={self.H}: use engine='chain'")
+
+    def _check_persistent(self) -> None:
+        """the preconditions of the persistent engine, or an exception"""
+        self._check_persistent_shape()
+        self._check_not_given_up()
+        if self._x_ok is None:
+            with torch.cuda.device(self.device):
+                self._x_ok = bool(_lib.load().opseq_xcd_supported(self.L, self.KX, self.H))
+        if not self._x_ok:
+            raise ValueError(f"engine='persistent' needs a whole MI355X (8 XCDs x 32 CUs visible) and the persistent stacked LSTM "
+                             f"switched on (OPSEQ_XCD); not so on {self.device}: use engine='chain'")
 
     # -- state --------------------------------------------------------------------------------
     def get_state(self, ids: Sequence[int]):
@@ -585,32 +622,103 @@ class LstmStackStreams(_StreamPool):
             h = h_n.to(device=self.device, dtype=torch.float32).transpose(0, 1)
             c = c_n.to(device=self.device, dtype=torch.float32).transpose(0, 1)
             rows = torch.stack([h, c], dim=2).reshape(n, self._row)
-            self.state.index_copy_(0, torch.from_numpy(idx).to(self.device), rows)
+            dst = torch.from_numpy(idx).to(self.device)
+            self._log_write(dst, rows)
+            self.state.index_copy_(0, dst, rows)
 
     # -- frames -------------------------------------------------------------------------------
     def _step_slots(self, slots: torch.Tensor, x: torch.Tensor, lengths: Optional[torch.Tensor] = None,
                     engine: Optional[str] = None) -> torch.Tensor:
         """x [n, k, 15, 5] -> y [n, k, 4], with the slot ids (and the lengths of a ragged call) already on the device
-        (int32 [n], checked by the caller) and x checked: no host synchronisation.  engine: None or "chain", the one there is"""
+        (int32 [n], checked by the caller) and x checked: no host synchronisation"""
         self._check_engine(engine, lengths)
-        n, k = int(x.shape[0]), int(x.shape[1])
-        S = self.slots_per_frame
-        m = self.model
-        lib = _lib.load()
         with torch.no_grad(), torch.cuda.device(self.device):
             x = x.contiguous().float()
-            stream = _stream_ptr(self.device)
-            if self._embed:      # relu(Linear 5 -> F) per slot, as NonLinearLstm.forward
-                feats = torch.empty((n, k, self.KX), dtype=torch.float32, device=self.device)
-                rc = lib.opseq_slot_embed_relu_f32(x.data_ptr(), m.boxes_linear.weight.data_ptr(), feats.data_ptr(), n * k, S,
-                                                   self.KX // S, stream)
-                _lib.check(rc, "opseq_slot_embed_relu_f32")
-            else:
-                feats = x
-            packed = m._runner._packed_weights(m._runner.weights(m.video_LSTM, m.predictions_layer), self.device, stream)
-            ws = self._ws.get(stream, (n, k), self.device, (lib.opseq_stream_workspace_bytes, n, k, self.L, self.KX, self.H))
-            y = torch.empty((n, k, 4), dtype=torch.float32, device=self.device)
-            call_entry("opseq_stream_step_f32",
-                            [feats.data_ptr(), slots.data_ptr(), self.state.data_ptr(), packed.data_ptr(), y.data_ptr(),
-                             ws.data_ptr(), ws.numel(), n, k, self.capacity, self.L, self.KX, self.H, stream], lengths, 2)
+            if check_engine(engine, self.engine) == "persistent":
+                return self._step_persistent(slots, x)
+            self._prune_log()
+            before = self.state.index_select(0, slots.long()) if len(self._log) else None
+            (y,) = self._step_chain(slots, x, lengths)
+            if before is not None:
+                self._log.record(slots, before, ("step", slots, x, lengths, y))
+        return y
+
+    def _features(self, x: torch.Tensor, stream: int) -> torch.Tensor:
+        """the LSTM stack's input rows [n, k, KX] of frames x [n, k, 15, 5]: NonLinearLstm's relu(Linear 5 -> F) per slot, as
+        NonLinearLstm.forward (in front of either engine; a replayed step starts from x again); BaselineLstm's are x itself"""
+        if not self._embed:
+            return x
+        n, k = int(x.shape[0]), int(x.shape[1])
+        S = self.slots_per_frame
+        feats = torch.empty((n, k, self.KX), dtype=torch.float32, device=self.device)
+        rc = _lib.load().opseq_slot_embed_relu_f32(x.data_ptr(), self.model.boxes_linear.weight.data_ptr(), feats.data_ptr(),
+                                                   n * k, S, self.KX // S, stream)
+        _lib.check(rc, "opseq_slot_embed_relu_f32")
+        return feats
+
+    def _step_chain(self, slots: torch.Tensor, x: torch.Tensor, lengths: Optional[torch.Tensor], out=None):
+        """the launch-per-step engine (opseq_stream_step_f32); out: (y,) to fill instead of a new tensor.  Returns (y,)."""
+        n, k = int(x.shape[0]), int(x.shape[1])
+        m = self.model
+        lib = _lib.load()
+        stream = _stream_ptr(self.device)
+        feats = self._features(x, stream)
+        packed = m._runner._packed_weights(m._runner.weights(m.video_LSTM, m.predictions_layer), self.device, stream)
+        ws = self._ws.get(stream, (n, k), self.device, (lib.opseq_stream_workspace_bytes, n, k, self.L, self.KX, self.H))
+        direct = out is not None and out[0].is_contiguous()
+        y = out[0] if direct else torch.empty((n, k, 4), dtype=torch.float32, device=self.device)
+        call_entry("opseq_stream_step_f32",
+                        [feats.data_ptr(), slots.data_ptr(), self.state.data_ptr(), packed.data_ptr(), y.data_ptr(),
+                         ws.data_ptr(), ws.numel(), n, k, self.capacity, self.L, self.KX, self.H, stream], lengths, 2)
+        if out is not None and not direct:
+            out[0].copy_(y)
+        return (y,) if out is None else out
+
+    def _step_persistent(self, slots: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
+        """the same step as one persistent launch per piece (opseq_stream_step_x_f32): pieces of at most
+        opseq_stream_x_max_streams(L) streams, and of as many frames as one workspace holds (chunk invariance makes the cut
+        in time exact).  Every launch is watched by the runner's monitor and logged for replay."""
+        n, k = int(x.shape[0]), int(x.shape[1])
+        m = self.model
+        lib = _lib.load()
+        L, KX, H = self.L, self.KX, self.H
+        nmax = int(lib.opseq_stream_x_max_streams(L))
+        kmax = k
+        while kmax > 1 and lib.opseq_stream_x_workspace_bytes(min(n, nmax), kmax, L, KX, H) == 0:
+            kmax = (kmax + 1) // 2
+        stream = _stream_ptr(self.device)
+        xpacked = m._runner._x_packed_weights(m._runner.weights(m.video_LSTM, m.predictions_layer), self.device, stream)
+        w_head = m.predictions_layer.weight
+        y = torch.empty((n, k, 4), dtype=torch.float32, device=self.device)
+        self._prune_log()
+        for lo in range(0, n, nmax):
+            hi = min(n, lo + nmax)
+            nn = hi - lo
+            sl = slots[lo:hi]
+            for t0 in range(0, k, kmax):
+                t1 = min(k, t0 + kmax)
+                kk = t1 - t0
+                whole = kk == k
+                xx = x[lo:hi] if whole else x[lo:hi, t0:t1].contiguous()
+                yy = y[lo:hi] if whole else torch.empty((nn, kk, 4), dtype=torch.float32, device=self.device)
+                if self._gave_up:    # found by a watch of this very loop: the rest of the call runs on the chain, unlogged
+                    self._step_chain(sl, xx, None, (yy,))
+                    if not whole:
+                        y[lo:hi, t0:t1].copy_(yy)
+                    continue
+                feats = self._features(xx, stream)
+                ws = self._xws.get(stream, (nn, kk), self.device, (lib.opseq_stream_x_workspace_bytes, nn, kk, L, KX, H))
+                entry = self._log.record(sl, self.state.index_select(0, sl.long()), ("step", sl, xx, None, yy))
+                _lib.check(lib.opseq_stream_step_x_f32(feats.data_ptr(), sl.data_ptr(), self.state.data_ptr(),
+                                                       xpacked.data_ptr(), w_head.data_ptr(), yy.data_ptr(), ws.data_ptr(),
+                                                       ws.numel(), nn, kk, self.capacity, L, KX, H, stream),
+                           "opseq_stream_step_x_f32")
+                entry.redo = lambda e=entry: self._heal(e)
+                self._launch_monitor().watch(ws, lib.opseq_stream_x_status_offset(nn, kk, L, KX, H), entry.redo,
+                                             "opseq_stream_step_x")
+                if not whole:        # a piece in time -> its place in the caller's tensor, again after a replay of the piece
+                    def place(yv=y[lo:hi, t0:t1], yy=yy):
+                        yv.copy_(yy)
+                    place()
+                    self.log_followup(place)
         return y

@@ -17,8 +17,8 @@ NonLinearLstm: one ragged call (host lengths, and an int32 device tensor), the s
 (one per k, each over the streams with that many frames), and a uniform call of k = 3 over all n.  device_us: HIP events
 around the window; wall_us: the window's wall time to the last call's completion, per call.
 
---engine persistent times OPNetStreams' persistent engine (one persistent launch a call) in place of the launch
-chain; --engine both times the two in alternating windows (--rounds of them each) and reports every window, the minimum and
+--engine persistent times the pool's persistent engine (one persistent launch a call: OPNetStreams, DESIGN.md 12e;
+LstmStackStreams for --model baseline_lstm / non_linear_lstm) in place of the launch chain; --engine both times the two in alternating windows (--rounds of them each) and reports every window, the minimum and
 the spread, per (n, k): stream_k{k} then holds {"chain": ..., "persistent": ..., "persistent_over_chain": ...}.
 
     python tools/stream_bench.py [--model opnet] [--ns 1,32,256] [--ks 1,8,300] [--engine chain] [--out result.json]
@@ -65,7 +65,7 @@ def main():
     ap.add_argument("--ns", default="1,32,256")
     ap.add_argument("--ks", default="1,8,300")
     ap.add_argument("--out", default=None)
-    ap.add_argument("--engine", default="chain", choices=["chain", "persistent", "both"], help="OPNetStreams engine (opnet)")
+    ap.add_argument("--engine", default="chain", choices=["chain", "persistent", "both"], help="the stream pool's engine")
     ap.add_argument("--rounds", type=int, default=3, help="--engine both: alternating windows per engine")
     ap.add_argument("--ragged", action="store_true", help="time ragged ticks (lengths 1, 2, 3) for all three models")
     args = ap.parse_args()
@@ -183,13 +183,18 @@ def bench_stack(args):
             r.use_xcd = "auto"
             row["whole_clip_default"] = _time(lambda: m(x5), 5, warmup=2)
             row["whole_clip_default_engine"] = r.engine(n, T)
+        r._monitor.verify()
         streams = LstmStackStreams(m, capacity=n)
         ids = streams.open(n)
         for k in ks:
             x = x5[:, :k].contiguous()
             calls = max(5, min(200, 1200 // k))
-            row[f"stream_k{k}"] = _time(lambda: streams.step(ids, x), calls)
+            if args.engine == "both":
+                row[f"stream_k{k}"] = _alternate(streams, ids, x, calls, args.rounds)
+                continue
+            row[f"stream_k{k}"] = _time(lambda: streams.step(ids, x, engine=args.engine), calls)
             row[f"stream_k{k}"]["device_us_per_frame"] = round(row[f"stream_k{k}"]["device_us"] / k, 2)
+            row["launches_gave_up"] = row.get("launches_gave_up", 0) + streams.verify_launches()
         # the one-frame call straight through the C ABI with every buffer prepared (NonLinearLstm: its layer-0 input already
         # embedded): the LSTM's kernels without the Python work of LstmStackStreams.step
         if 1 in ks:
@@ -204,14 +209,14 @@ def bench_stack(args):
                                                      packed.data_ptr(), y1.data_ptr(), ws.data_ptr(), ws.numel(), n, 1, n, L, KX,
                                                      H, stream), "opseq_stream_step_f32")
             row["abi_k1"] = _time(abi_call, 200)
-        if 300 in ks:
+        if 300 in ks and args.engine != "both":
             row["k300_over_chain"] = round(row["stream_k300"]["device_us"] / row["whole_clip_chain"]["device_us"], 3)
-        if 1 in ks:
+        if 1 in ks and args.engine != "both":
             row["prefix_speedup_at_t300"] = round(row["whole_clip_default"]["device_us"] / row["stream_k1"]["device_us"], 1)
             row["prefix_speedup_vs_chain_at_t300"] = round(row["whole_clip_chain"]["device_us"] / row["stream_k1"]["device_us"], 1)
         res["rows"].append(row)
         print(json.dumps(row), file=sys.stderr, flush=True)
-    if args.model == "non_linear_lstm":
+    if args.model == "non_linear_lstm" and args.engine == "chain":
         res["input_product"] = bench_input_product(m, dev)
     return res
 
