@@ -105,7 +105,8 @@ int opnet_xcd_profile_read(double *kernel_ms_total, int *launches);
 /* the same for the other profiled kernels while opnet_xcd_profile(1) is on: tag 0 = opnet_xcd_forward, 1 = seqx_forward (the
  * persistent stacked LSTM), 2 = the attention kernel(s) of an encoder layer's attention call, 3 = seqt_forward, 4 = the fused
  * feed-forward kernel of an encoder layer, 5 / 6 = the flash attention launches of an encoder layer's TRAINING forward / backward
- * (csrc/attn_train_kernels.hip), 7 = seqx_backward (the stacked LSTM's reverse recurrence as one launch) */
+ * (csrc/attn_train_kernels.hip), 7 = seqx_backward (the stacked LSTM's reverse recurrence as one launch), 8 = opnet_dboxes (the
+ * box gradient of opnet_train_backward_ex_f32) */
 int opnet_kernel_profile_read(int tag, double *kernel_ms_total, int *launches);
 /* tools: device buffer of >= (T+1) * ceil(B/128) * 8 uint64 receiving s_memtime stamps of block 0 (NULL = off) */
 void opnet_xcd_set_trace(void *device_buffer);
@@ -148,8 +149,8 @@ int opnet_xcd4_enabled(void);
  * slot probabilities and frames_boxes in `workspace` (5.7 MB/clip at T=300, plus 64 MB whatever the batch: the partial
  * tiles of the weight-gradient waves).
  * opnet_train_backward_f32 consumes that history and dy = dLoss/dy_boxes [B,T,4] and writes the six
- * weight gradients in the state_dict layouts (`boxes` never requires grad; the logits output is not
- * differentiated - no reference loss uses it, training_main.py:186-210).  `packed` must come from
+ * weight gradients in the state_dict layouts (no gradient for `boxes` and none through the logits output - no reference
+ * loss uses it, training_main.py:186-210; opnet_train_backward_ex_f32 below adds both).  `packed` must come from
  * opnet_train_pack_weights_f32 (inference tiles + transposed tiles for the backward recurrence).
  * One workspace holds ONE forward's history: call backward before the next train forward.
  * On a whole MI355X at the reference hidden sizes batches of up to 32 clips run both recurrences as one persistent launch each
@@ -168,6 +169,29 @@ int opnet_train_forward_f32(const float *boxes, const float *packed, float *y, f
 int opnet_train_backward_f32(const float *dy, const float *packed, void *workspace, size_t workspace_bytes,
                              float *g_ih1, float *g_hh1, float *g_sel, float *g_ih2, float *g_hh2,
                              float *g_out, int B, int T, int H1, int H2, void *stream);
+/* The backward with the two opt-in extras (both may be NULL; with both NULL the call IS opnet_train_backward_f32):
+ *   dlogits [B,15,T]   in:  an upstream gradient of the selection logits (a loss on "which slot to track").  It is added to
+ *                           the softmax backward's own logit gradient before that reaches object_to_track_LSTM, so all six
+ *                           weight gradients contain it.
+ *   dboxes  [B,T,15,6] out: the gradient of the input boxes,
+ *                           p_t[o] * (W_ih2^T da2_t)[f] + sum_r W_ih1[r][6 o + f] * da1_t[r].
+ * `extra` is a second caller-owned device workspace of opnet_train_extra_workspace_bytes(B, T, H1, H2) bytes (16-byte
+ * aligned; the packed logit gradient, the per-step d frames_boxes and the W_ih1^T tiles of the box-gradient product, which
+ * are made from `packed` by every call that asks for dboxes).  The training workspace and its size do not change.
+ * A call with an extra runs the reverse recurrence on the launch chain at every batch size (the persistent reverse
+ * recurrence carries neither extra).  If the step's persistent forward gave up, dboxes is NaN like the weight gradients. */
+size_t opnet_train_extra_workspace_bytes(int B, int T, int H1, int H2);
+int opnet_train_backward_ex_f32(const float *dy, const float *packed, void *workspace, size_t workspace_bytes,
+                                float *g_ih1, float *g_hh1, float *g_sel, float *g_ih2, float *g_hh2, float *g_out,
+                                int B, int T, int H1, int H2, const float *dlogits, float *dboxes, void *extra,
+                                size_t extra_bytes, void *stream);
+/* Mean cross-entropy of the selection logits [B,15,T] against one slot index per (b, t): targets [B,T], int32 or (targets_i64
+ * != 0) int64 - torch.nn.functional.cross_entropy(logits, targets, ignore_index=...) - and its gradient dlogits [B,15,T] (may
+ * be NULL), with the softmax recomputed from the logits.  The mean runs over the targets != ignore_index; none at all gives
+ * loss 0 and gradient 0.  A target outside [0,15) that is not ignore_index makes loss and gradient NaN.  scratch: >= 16 KB of
+ * device memory, 8-byte aligned.  Fixed-order reduction: the same bits on every run. */
+int opnet_selection_ce_f32(const float *logits, const void *targets, int targets_i64, long ignore_index, float *loss,
+                           float *dlogits, int B, int T, void *scratch, size_t scratch_bytes, void *stream);
 /* loss = mean(|y - labels|) over n elements (nn.L1Loss(reduction="none") + torch.mean); dy (may be NULL)
  * = sign(y - labels) / n.  scratch: >= 4096 bytes of device memory. Deterministic reduction. */
 int opnet_l1_loss_f32(const float *y, const float *labels, float *loss, float *dy, long n, void *scratch,
@@ -246,6 +270,11 @@ int opnet_mlp_train_forward_f32(const float *boxes, const float *packed, float *
 int opnet_mlp_train_backward_f32(const float *dy, const float *packed, void *workspace, size_t workspace_bytes,
                                  float *g_ih1, float *g_hh1, float *g_sel, float *g_hidden_scratch, float *g_out,
                                  int B, int T, int H1, int H2, void *stream);
+/* ... with the extras of opnet_train_backward_ex_f32 (same meaning, same `extra` workspace and size query) */
+int opnet_mlp_train_backward_ex_f32(const float *dy, const float *packed, void *workspace, size_t workspace_bytes,
+                                    float *g_ih1, float *g_hh1, float *g_sel, float *g_hidden_scratch, float *g_out,
+                                    int B, int T, int H1, int H2, const float *dlogits, float *dboxes, void *extra,
+                                    size_t extra_bytes, void *stream);
 
 /* ---- stateful streams: OPNet / OPNetLstmMlp with the LSTM state carried across calls ---------------------
  * A call advances n streams by k >= 1 frames each.  A stream's state is a row of the caller-owned pool

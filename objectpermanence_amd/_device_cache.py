@@ -121,8 +121,9 @@ class TrainingBuffers:
     the owner's latest forward.  The image is re-packed by every forward."""
 
     def __init__(self):
-        self.image = self.history = None
+        self.image = self.history = self.extra = None
         self.key = None          # (B, T, device index) of the history
+        self.extra_key = None    # ... of the second workspace of a backward with extras (made on first use)
 
     def packed(self, device: torch.device, nbytes, pack, zero: bool = False) -> torch.Tensor:
         size = _size(nbytes)
@@ -139,3 +140,12 @@ class TrainingBuffers:
             self.history = _new(size, torch.uint8, device)
             self.key = key
         return self.history
+
+    def extra_for(self, B: int, T: int, device: torch.device, nbytes) -> torch.Tensor:
+        key = (B, T, device_index(device))
+        if self.extra_key != key:
+            size = _size(nbytes)
+            self.extra = None
+            self.extra = _new(size, torch.uint8, device)
+            self.extra_key = key
+        return self.extra

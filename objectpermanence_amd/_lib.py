@@ -85,6 +85,12 @@ def _declare(lib):
     lib.opnet_train_backward_f32.restype = c_int
     lib.opnet_train_backward_f32.argtypes = [fp, fp, c_void_p, c_size_t, fp, fp, fp, fp, fp, fp,
                                              c_int, c_int, c_int, c_int, c_void_p]
+    lib.opnet_train_extra_workspace_bytes.restype = c_size_t
+    lib.opnet_train_extra_workspace_bytes.argtypes = [c_int, c_int, c_int, c_int]
+    lib.opnet_train_backward_ex_f32.restype = c_int
+    lib.opnet_train_backward_ex_f32.argtypes = lib.opnet_train_backward_f32.argtypes[:-1] + [fp, fp, c_void_p, c_size_t, c_void_p]
+    lib.opnet_selection_ce_f32.restype = c_int
+    lib.opnet_selection_ce_f32.argtypes = [fp, fp, c_int, ctypes.c_long, fp, fp, c_int, c_int, c_void_p, c_size_t, c_void_p]
     lib.opnet_l1_loss_f32.restype = c_int
     lib.opnet_l1_loss_f32.argtypes = [fp, fp, fp, fp, ctypes.c_long, c_void_p, c_size_t, c_void_p]
     lib.opnet_smooth_l1_loss_f32.restype = c_int
@@ -138,6 +144,9 @@ def _declare(lib):
     lib.opnet_mlp_train_backward_f32.restype = c_int
     lib.opnet_mlp_train_backward_f32.argtypes = [fp, fp, c_void_p, c_size_t, fp, fp, fp, fp, fp,
                                                  c_int, c_int, c_int, c_int, c_void_p]
+    lib.opnet_mlp_train_backward_ex_f32.restype = c_int
+    lib.opnet_mlp_train_backward_ex_f32.argtypes = lib.opnet_mlp_train_backward_f32.argtypes[:-1] + [fp, fp, c_void_p, c_size_t,
+                                                                                                     c_void_p]
     lib.opseq_lstm_stack_packed_bytes.restype = c_size_t
     lib.opseq_lstm_stack_packed_bytes.argtypes = [c_int, c_int, c_int]
     lib.opseq_lstm_stack_workspace_bytes.restype = c_size_t
@@ -346,7 +355,8 @@ EXPORTS = [
     "opnet_xcd4_workspace_bytes", "opnet_xcd4_pack_weights_f32", "opnet_xcd4_forward_f32",
     "opnet_xcd_profile", "opnet_xcd_profile_read", "opnet_kernel_profile_read",
     "opnet_train_packed_weights_bytes", "opnet_train_pack_weights_f32", "opnet_train_workspace_bytes",
-    "opnet_train_forward_f32", "opnet_train_backward_f32", "opnet_l1_loss_f32", "opnet_smooth_l1_loss_f32", "opnet_adam_step_f32", "opnet_adam_multi_step_f32",
+    "opnet_train_forward_f32", "opnet_train_backward_f32", "opnet_train_extra_workspace_bytes", "opnet_train_backward_ex_f32",
+    "opnet_selection_ce_f32", "opnet_l1_loss_f32", "opnet_smooth_l1_loss_f32", "opnet_adam_step_f32", "opnet_adam_multi_step_f32",
     "opnet_adam_multi_step_guarded_f32", "opnet_dp_guard_f32", "opnet_xcd4_status_offset", "opnet_train_status_offset", "opnet_xcd4_enable", "opnet_xcd4_enabled",
     "opnet_mlp_pack_weights_f32", "opnet_mlp_forward_f32",
     "opnet_stream_state_floats", "opnet_stream_workspace_bytes", "opnet_stream_step_f32", "opnet_stream_step_ragged_f32",
@@ -354,6 +364,7 @@ EXPORTS = [
     "opnet_stream_step_x4_f32",
     "opnet_online_encode_f32", "opnet_online_encode_ragged_f32",
     "opnet_mlp_train_pack_weights_f32", "opnet_mlp_train_forward_f32", "opnet_mlp_train_backward_f32",
+    "opnet_mlp_train_backward_ex_f32",
     "opseq_lstm_stack_packed_bytes", "opseq_lstm_stack_workspace_bytes", "opseq_lstm_stack_pack_weights_f32",
     "opseq_lstm_stack_forward_f32", "opseq_lstm_stack_forward_graph_f32", "opseq_graph_cache_clear",
     "opseq_stream_state_floats", "opseq_stream_workspace_bytes", "opseq_stream_step_f32", "opseq_stream_step_ragged_f32",

@@ -446,7 +446,8 @@ static int g_xcd_cus[64] = {};
 #define PROF_ATTN_TF 5      // training attention, forward: attention_train_fwd (+ merge) of one layer call (csrc/attn_train_kernels.hip)
 #define PROF_ATTN_TB 6      // training attention, backward: prep + the dQ pass + the dK / dV pass (+ reduces) of one layer call
 #define PROF_SEQXB 7        // seqx_backward: the stacked LSTM's reverse recurrence as one launch (csrc/seq_xcd_bwd_kernels.hip)
-#define PROF_TAGS 8
+#define PROF_DBOXES 8       // opnet_dboxes: the box gradient of a training backward with extras (csrc/opnet_train_kernels.hip)
+#define PROF_TAGS 9
 typedef std::pair<hipEvent_t, hipEvent_t> ProfPair;
 static bool g_xcd_prof = false;
 static std::vector<ProfPair> g_prof_ev[PROF_TAGS];
@@ -1421,9 +1422,58 @@ static bool wgrad_wave_tiles(const WgradArgs *jobs, int njobs, int T, int RB, in
     return true;
 }
 
+// the opt-in extras of a backward (opnet_train_backward_ex_f32): both null = the plain step
+struct TrainExtras {
+    const float *dlogits;   // [B][15][T] upstream gradient of the selection logits
+    float *dboxes;          // [B][T][15][6] out: gradient of the input boxes
+    void *extra;            // the caller's second workspace (extra_workspace_layout)
+    size_t extra_bytes;
+};
+
 static int train_backward_impl(const float *dy, const float *packed, void *workspace, size_t workspace_bytes,
                                float *g_ih1, float *g_hh1, float *g_sel, float *g_ih2, float *g_hh2, float *g_out,
-                               int B, int T, int H1, int H2, void *stream, int mlp);
+                               int B, int T, int H1, int H2, void *stream, int mlp, const TrainExtras *ex = nullptr);
+
+// second workspace of a backward with extras; the training workspace itself is unchanged
+struct ExtraWorkspaceLayout { size_t dlin, dfball, wih1t, total; };   // offsets in bytes
+static ExtraWorkspaceLayout extra_workspace_layout(int B, int T, int H1)
+{
+    const size_t RB = (B + 31) / 32, TT = T;
+    ExtraWorkspaceLayout L;
+    size_t o = 0;
+    L.dlin = o;   o += TT * RB * 128 * 16;                   // [T][RB][4][32] float4, dlall's layout
+    L.dfball = o; o += TT * RB * 64 * 16;                    // [T][RB][2][32] float4, x2all's layout
+    L.wih1t = o;  o += (size_t)6 * (H1 / 4) * 256 * 4;       // W_ih1^T tiles of opnet_dboxes
+    L.total = align_up(o, 256);
+    return L;
+}
+
+extern "C" size_t opnet_train_extra_workspace_bytes(int B, int T, int H1, int H2)
+{
+    if (check_dims(B, T, H1, H2)) return 0;
+    return extra_workspace_layout(B, T, H1).total;
+}
+
+extern "C" int opnet_train_backward_ex_f32(const float *dy, const float *packed, void *workspace, size_t workspace_bytes,
+                                           float *g_ih1, float *g_hh1, float *g_sel, float *g_ih2, float *g_hh2, float *g_out,
+                                           int B, int T, int H1, int H2, const float *dlogits, float *dboxes, void *extra,
+                                           size_t extra_bytes, void *stream)
+{
+    if (!g_hh2) return fail(OPNET_EINVAL, "null pointer");
+    const TrainExtras ex{dlogits, dboxes, extra, extra_bytes};
+    return train_backward_impl(dy, packed, workspace, workspace_bytes, g_ih1, g_hh1, g_sel, g_ih2, g_hh2, g_out, B, T,
+                               H1, H2, stream, 0, &ex);
+}
+
+extern "C" int opnet_mlp_train_backward_ex_f32(const float *dy, const float *packed, void *workspace, size_t workspace_bytes,
+                                               float *g_ih1, float *g_hh1, float *g_sel, float *g_hidden_scratch, float *g_out,
+                                               int B, int T, int H1, int H2, const float *dlogits, float *dboxes, void *extra,
+                                               size_t extra_bytes, void *stream)
+{
+    const TrainExtras ex{dlogits, dboxes, extra, extra_bytes};
+    return train_backward_impl(dy, packed, workspace, workspace_bytes, g_ih1, g_hh1, g_sel, g_hidden_scratch, nullptr,
+                               g_out, B, T, H1, H2, stream, 1, &ex);
+}
 
 extern "C" int opnet_train_backward_f32(const float *dy, const float *packed, void *workspace,
                                         size_t workspace_bytes, float *g_ih1, float *g_hh1, float *g_sel,
@@ -1447,20 +1497,33 @@ extern "C" int opnet_mlp_train_backward_f32(const float *dy, const float *packed
 
 static int train_backward_impl(const float *dy, const float *packed, void *workspace, size_t workspace_bytes,
                                float *g_ih1, float *g_hh1, float *g_sel, float *g_ih2, float *g_hh2, float *g_out,
-                               int B, int T, int H1, int H2, void *stream, int mlp)
+                               int B, int T, int H1, int H2, void *stream, int mlp, const TrainExtras *ex)
 {
     StepArgs a; OpnetIO io; BwdArgs bw;
     if (!dy || !g_ih1 || !g_hh1 || !g_sel || !g_ih2 || !g_out) return fail(OPNET_EINVAL, "null pointer");
     if (!aligned16(dy)) return fail(OPNET_EINVAL, "dy must be 16-byte aligned");
     if (int rc = make_train_args(&a, &io, &bw, nullptr, packed, nullptr, nullptr, workspace, workspace_bytes, B, T, H1, H2))
         return rc;
+    // extras: a gradient entering through the selection logits and / or the gradient of the input boxes
+    const bool extras = ex && (ex->dlogits || ex->dboxes);
+    const ExtraWorkspaceLayout E = extra_workspace_layout(B, T, H1);
+    if (extras) {
+        if (!ex->extra || !aligned16(ex->extra)) return fail(OPNET_EINVAL, "extra workspace must be a 16-byte aligned device buffer");
+        if (ex->extra_bytes < E.total) return fail(OPNET_EWORKSPACE, "extra workspace %zu B < %zu B", ex->extra_bytes, E.total);
+        if (ex->dlogits) bw.dlin = (const float4 *)((char *)ex->extra + E.dlin);
+        if (ex->dboxes) bw.dfball = (float4 *)((char *)ex->extra + E.dfball);
+    }
     const TrainWorkspaceLayout W = train_workspace_layout(B, T, H1, H2);
     hipStream_t st = (hipStream_t)stream;
     const int RB = a.RB;
     char *w = (char *)workspace;
     // (33 .. 64 clips as one 4-clip persistent launch per row block, one after the other: measured 2.30 ms against 2.19 for the
     // two chains of fused steps below - not adopted)
-    const bool x4_bwd = !mlp && x4_use(B, T, H1, H2) && env_int("OPNET_XCD4_BWD", 1) != 0;
+    // (a step with extras runs the launch chain: the persistent reverse recurrence neither takes a logit gradient nor keeps
+    // d frames_boxes - the route of a 33 .. 96-clip step, whose forward is the 4-clip persistent launch too)
+    const bool x4_bwd = !mlp && !extras && x4_use(B, T, H1, H2) && env_int("OPNET_XCD4_BWD", 1) != 0;
+    if (extras && ex->dlogits)
+        opnet_pack_dlogits<<<256, 256, 0, st>>>(ex->dlogits, (float4 *)((char *)ex->extra + E.dlin), B, T, RB);
     if (!x4_bwd)        // (the 4-clip persistent form packs dy in its own initialisation launch)
         opnet_pack_dy<<<256, 256, 0, st>>>((const float4 *)dy, (float4 *)(w + W.dyp), (float *)(w + W.dcz),
                                             (long)((W.dcz_end - W.dcz) / 4), B, T, RB);
@@ -1566,6 +1629,23 @@ static int train_backward_impl(const float *dy, const float *packed, void *works
     }
     // a forward or reverse recurrence that gave up (4-clip persistent kernels) left partial histories: every dW becomes NaN
     wb.abort = train_status_offset(W, B, T, H1, H2) != (size_t)-1 ? (const unsigned *)(w + train_status_offset(W, B, T, H1, H2)) : nullptr;
+    if (extras && ex->dboxes) {
+        // d boxes = p (x) d frames_boxes + W_ih1^T da1 over the histories the recurrence left (opnet_dboxes); the W_ih1^T tiles are
+        // made from the forward image for this call (9 .. 400 KB: no cache to invalidate)
+        const PackedLayout P = packed_layout(H1, H2);
+        float *wt = (float *)((char *)ex->extra + E.wih1t);
+        const size_t nwt = (size_t)6 * (H1 / 4) * 256;
+        opnet_pack_wih1t<<<(unsigned)((nwt + 255) / 256 > 1024 ? 1024 : (nwt + 255) / 256), 256, 0, st>>>(wt, packed + P.w1p, H1);
+        DboxArgs d;
+        d.B = B; d.T = T; d.RB = RB; d.H1 = H1;
+        d.g1 = bw.g1; d.wt = (const float4 *)wt; d.psave = bw.psave; d.dfball = bw.dfball;
+        d.dboxes = ex->dboxes; d.abort = wb.abort;
+        const long nitems = (long)T * RB;
+        ProfPair pe;
+        const bool prof = prof_begin(st, &pe);
+        opnet_dboxes<<<(unsigned)(nitems > 4096 ? 4096 : nitems), 64 * DBOX_NW, 0, st>>>(d);
+        if (prof) prof_end(PROF_DBOXES, st, pe);
+    }
     if (wgrad_wave_tiles(wb.job, njobs, T, RB, B, (float *)(w + W.wgpart), wb.abort, st)) {
         HIP_TRY(hipGetLastError());
         return OPNET_OK;
@@ -1621,7 +1701,9 @@ extern "C" int opnet_mlp_train_forward_f32(const float *boxes, const float *pack
     OpnetIO *dio = (OpnetIO *)((char *)workspace + W.io);
     opnet_set_io<<<1, 1, 0, st>>>(dio, io);
     opnet_pack_input<<<dim3(T, a.RB), 256, 0, st>>>(dio);
-    if (x4_batch(B, H1, H2)) HIP_TRY(hipMemsetAsync((char *)workspace + W.x4status, 0, 32, st));   // (see opnet_train_forward_f32)
+    // (see opnet_train_forward_f32: the status words the backward's abort test and the optimiser's guard read - the 4-clip
+    // kernels' or, from 97 clips on, the 16-clip forward's; this forward never raises them, so it has to clear them)
+    if (train_status_offset(W, B, T, H1, H2) != (size_t)-1) HIP_TRY(hipMemsetAsync((char *)workspace + train_status_offset(W, B, T, H1, H2), 0, 32, st));
     const dim3 grid = step_grid(a);
     const opnet_step_fn stepk = step_kernel(a);
     for (int s = 0; s < T + 3; ++s) stepk<<<grid, step_threads(a), 0, st>>>(a, s);
@@ -1656,6 +1738,30 @@ static int l1_family(const float *y, const float *labels, float *loss, float *dy
     hipStream_t st = (hipStream_t)stream;
     opnet_l1_partial<<<nb, 256, 0, st>>>(y, labels, dy, (float *)scratch, n, beta);
     opnet_l1_final<<<1, 64, 0, st>>>((const float *)scratch, nb, loss, n);
+    HIP_TRY(hipGetLastError());
+    return OPNET_OK;
+}
+
+/* Mean cross-entropy of the selection logits [B,15,T] against targets [B,T] (int32, or int64 with targets_i64 != 0) over the
+ * targets != ignore_index, and its gradient dlogits [B,15,T] (may be null).  scratch: >= 16 KB of device memory, 8-byte aligned. */
+extern "C" int opnet_selection_ce_f32(const float *logits, const void *targets, int targets_i64, long ignore_index, float *loss,
+                                      float *dlogits, int B, int T, void *scratch, size_t scratch_bytes, void *stream)
+{
+    if (!logits || !targets || !loss || !scratch) return fail(OPNET_EINVAL, "null pointer");
+    if (B <= 0 || T <= 0) return fail(OPNET_ESHAPE, "B and T must be positive");
+    if (((uintptr_t)scratch) & 7u) return fail(OPNET_EINVAL, "scratch must be 8-byte aligned");
+    const long n = (long)B * T;
+    const int nb = (int)((n + 255) / 256 > 1024 ? 1024 : (n + 255) / 256);
+    // [1024 double partial sums][1024 counts][1 / count]
+    const size_t need = 1024 * 8 + 1024 * 4 + 16;
+    if (scratch_bytes < need) return fail(OPNET_EWORKSPACE, "scratch %zu B < %zu B", scratch_bytes, need);
+    double *psum = (double *)scratch;
+    unsigned *pcnt = (unsigned *)((char *)scratch + 1024 * 8);
+    float *inv = (float *)((char *)scratch + 1024 * 8 + 1024 * 4);
+    hipStream_t st = (hipStream_t)stream;
+    opnet_sel_ce_partial<<<nb, 256, 0, st>>>(logits, targets, targets_i64, ignore_index, psum, pcnt, B, T);
+    opnet_sel_ce_final<<<1, 64, 0, st>>>(psum, pcnt, nb, loss, inv);
+    if (dlogits) opnet_sel_ce_grad<<<nb, 256, 0, st>>>(logits, targets, targets_i64, ignore_index, inv, dlogits, B, T);
     HIP_TRY(hipGetLastError());
     return OPNET_OK;
 }

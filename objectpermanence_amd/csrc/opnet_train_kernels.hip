@@ -49,6 +49,9 @@ struct BwdArgs {
     const float4 *wih2t;    // [4*H2/16][64]         W_ih2^T (6 -> 16 rows)
     const float *wsel;      // [15][H1] raw
     const float *wout;      // [4][H2] raw
+    // opt-in extras (null = off: the plain step): gradients through the selection logits and to the input boxes
+    const float4 *dlin;     // [T][RB][4][32]  upstream gradient of the selection logits, packed like dlall - added to dl_t
+    float4 *dfball;         // [T][RB][2][32]  d frames_boxes_t = W_ih2^T da2_t kept per step, in x2all's layout (6 of 8 floats written)
 };
 
 // ------------------------------------------------------------------------------------------------
@@ -103,6 +106,27 @@ __global__ void __launch_bounds__(256) opnet_pack_dy(const float4 *__restrict__ 
         dyp[idx] = b < B ? dy[(long)b * T + t] : make_float4(0.f, 0.f, 0.f, 0.f);
     }
     for (long idx = blockIdx.x * (long)blockDim.x + threadIdx.x; idx < n_dc; idx += stride) dc_zero[idx] = 0.f;
+}
+
+// dlogits [B][15][T] -> dlin [T][RB][4][32] float4 (dlall's layout: slot o in quad o / 4, element o % 4); slot 15 and the clips
+// beyond B are zero
+__global__ void __launch_bounds__(256) opnet_pack_dlogits(const float *__restrict__ dlg, float4 *__restrict__ dlin, int B, int T, int RB)
+{
+    const long n = (long)T * RB * 128;
+    for (long idx = blockIdx.x * (long)blockDim.x + threadIdx.x; idx < n; idx += (long)gridDim.x * blockDim.x) {
+        const int clip = idx & 31, q = (idx >> 5) & 3;
+        const long trb = idx >> 7;
+        const int rb = trb % RB;
+        const int t = trb / RB;
+        const int b = rb * 32 + clip;
+        float v[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int o = 4 * q + e;
+            v[e] = (b < B && o < OPNET_SLOTS_) ? dlg[((long)b * OPNET_SLOTS_ + o) * T + t] : 0.f;
+        }
+        dlin[idx] = make_float4(v[0], v[1], v[2], v[3]);
+    }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -247,14 +271,26 @@ __global__ void __launch_bounds__(256) opnet_bwd_cell(const BwdArgs a, const int
             }
             float dl[16];
 #pragma unroll
-            for (int o = 0; o < 16; ++o) {
-                dl[o] = o < OPNET_SLOTS_ ? p[o] * (dp[o] - dot) : 0.f;
-                dl_s[clip][o] = dl[o];
+            for (int o = 0; o < 16; ++o) dl[o] = o < OPNET_SLOTS_ ? p[o] * (dp[o] - dot) : 0.f;
+            if (a.dlin) {   // a loss on the logits themselves: dlall then holds the total, which is what W_sel's gradient needs
+                const float4 *up = a.dlin + ((long)t * a.RB + rb) * 128 + clip;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const float4 v = up[q * 32];
+                    dl[4 * q] += v.x; dl[4 * q + 1] += v.y; dl[4 * q + 2] += v.z; dl[4 * q + 3] += v.w;
+                }
             }
+#pragma unroll
+            for (int o = 0; o < 16; ++o) dl_s[clip][o] = dl[o];
             if (bx == nc2) {
                 float4 *dst = a.dlall + ((long)t * a.RB + rb) * 128 + clip;
 #pragma unroll
                 for (int q = 0; q < 4; ++q) dst[q * 32] = make_float4(dl[4 * q], dl[4 * q + 1], dl[4 * q + 2], dl[4 * q + 3]);
+                if (a.dfball) {
+                    float *dfb = (float *)(a.dfball + ((long)t * a.RB + rb) * 64);
+#pragma unroll
+                    for (int f = 0; f < OPNET_FEATS_; ++f) dfb[((f >> 2) * 32 + clip) * 4 + (f & 3)] = dx[f];
+                }
             }
         }
         __syncthreads();
@@ -467,6 +503,8 @@ __global__ void __launch_bounds__(FUSED_THREADS) opnet_bwd_fused(const BwdArgs a
             }
             const float dx = fused_product(a.wih2t, a.g2 + ((long)t * a.RB + rb) * H2 * 32, H2 >> 2, hf, part);
             if (owner && row < OPNET_FEATS_) dxs[row][cl] = dx;
+            if (a.dfball && owner && row < OPNET_FEATS_)
+                ((float *)(a.dfball + ((long)t * a.RB + rb) * 64))[((row >> 2) * 32 + c) * 4 + (row & 3)] = dx;
             __syncthreads();
             // einsum backward: dp[o] = sum_f boxes[o][f] dx[f]; softmax backward: dl = p * (dp - <p, dp>)
             float dp = 0.f;
@@ -485,7 +523,10 @@ __global__ void __launch_bounds__(FUSED_THREADS) opnet_bwd_fused(const BwdArgs a
             __syncthreads();
             if (owner) {
                 float *dst = (float *)(a.dlall + ((long)t * a.RB + rb) * 128);
-                dst[((o >> 2) * 32 + c) * 4 + (o & 3)] = o < OPNET_SLOTS_ ? pv * (dp - dots[cl]) : 0.f;
+                float dl = o < OPNET_SLOTS_ ? pv * (dp - dots[cl]) : 0.f;
+                // (a loss on the logits themselves: dlall then holds the total, which is what W_sel's gradient needs)
+                if (a.dlin) dl += ((const float *)(a.dlin + ((long)t * a.RB + rb) * 128))[((o >> 2) * 32 + c) * 4 + (o & 3)];
+                dst[((o >> 2) * 32 + c) * 4 + (o & 3)] = dl;
             }
             if (rb + (int)gridDim.y < a.rb1) __syncthreads();
         }
@@ -559,6 +600,112 @@ __global__ void __launch_bounds__(256) opnet_mlp_dhid(const BwdArgs a)
         // hidden_t sits in the h2 history slot t+1, kq-major: [(u/4)][clip][u%4]
         const float hid = ((const float *)(a.h2all + (((long)(t + 1)) * a.RB + rb) * ((long)H2 * 8)))[((long)(u >> 2) * 32 + clip) * 4 + (u & 3)];
         a.g2[idx] = make_float4(hid > 0.f ? dh : 0.f, 0.f, 0.f, 0.f);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// gradient of the input boxes (opt-in): one launch behind the reverse recurrence
+// ------------------------------------------------------------------------------------------------
+//     dboxes[b][t][o][f] = p_t[o] * d frames_boxes_t[f]  +  sum_r W_ih1[r][6 o + f] * da1_t[r]
+// (the einsum's box operand; LSTM1's input).  The second term is, per (t, row block), a [96 columns (90 valid) x 32 clips]
+// product over K = 4 H1 with da1_t read where the recurrence left it: g1 is already the kq-major activation layout with
+// k = 4 unit + gate.  W_ih1^T comes as six 16-column A tiles in the same k order (opnet_pack_wih1t, out of the forward image).
+// One workgroup per (t, row block): its four waves split K, each holds all 6 x 2 accumulators, so every da1 fragment is
+// loaded exactly once (the kernel's HBM traffic: 4 H1 x 16 B per clip and step); the 24 H1 KB of weight tiles are shared by
+// all workgroups and stay in the L2.  Partials meet in LDS in fixed wave order; the epilogue adds p (x) dfb and writes the
+// caller's [B][T][15][6] rows, nothing for padded clips.
+struct DboxArgs {
+    int B, T, RB, H1;
+    const float4 *g1;       // [T][RB][H1][32]   da1
+    const float4 *wt;       // [6][H1/4][64]     W_ih1^T tiles
+    const float4 *psave;    // [T][RB][4][32]
+    const float4 *dfball;   // [T][RB][2][32]
+    float *dboxes;          // [B][T][15][6]
+    const unsigned *abort;  // status word of the step's persistent forward (null: launch chain); nonzero -> dboxes is NaN
+};
+
+// out[ct][q][lane][e] = W_ih1[(k & 3) * H1 + (k >> 2)][16 ct + (lane & 15)], k = 16 q + 4 (lane >> 4) + e, read from the
+// forward's LSTM1 tiles (opnet_pack_tiles mode 0: tile = unit / 4, row (unit % 4) * 4 + gate; columns 90 .. 95 are zero there)
+__global__ void __launch_bounds__(256) opnet_pack_wih1t(float *__restrict__ out, const float *__restrict__ w1p, int H1)
+{
+    const int nq = H1 >> 2, nhex = (OPNET_KXQ * 4 + H1) >> 4;
+    const long total = 6L * nq * 256;
+    for (long idx = blockIdx.x * (long)blockDim.x + threadIdx.x; idx < total; idx += (long)gridDim.x * blockDim.x) {
+        const int e = idx & 3, lane = (idx >> 2) & 63;
+        const long tq = idx >> 8;
+        const int q = tq % nq, ct = tq / nq;
+        const int k = 16 * q + 4 * (lane >> 4) + e;
+        const int unit = k >> 2, gate = k & 3;
+        const int col = 16 * ct + (lane & 15);
+        out[idx] = w1p[((((long)(unit >> 2) * nhex + (col >> 4)) * 64) + ((unit & 3) * 4 + gate) + 16 * ((col & 15) >> 2)) * 4 + (col & 3)];
+    }
+}
+
+#define DBOX_NW 4
+__global__ void __launch_bounds__(64 * DBOX_NW) opnet_dboxes(const DboxArgs a)
+{
+    __shared__ float part[DBOX_NW][12][4][64];      // [wave][column tile * 2 + clip half][accumulator register][lane]
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int nq = a.H1 >> 2;                       // hexadecets of K = 4 H1
+    const int q0 = (w * nq) / DBOX_NW, q1 = ((w + 1) * nq) / DBOX_NW;
+    const int boff = ((lane >> 4) * 32 + (lane & 15)) * 16;
+    const __amdgpu_buffer_rsrc_t ra = frag_rsrc(a.wt);
+    const bool bad = a.abort && *a.abort != 0u;
+    const long nitems = (long)a.T * a.RB;
+    for (long item = blockIdx.x; item < nitems; item += gridDim.x) {
+        const __amdgpu_buffer_rsrc_t rs = frag_rsrc(a.g1 + item * a.H1 * 32);
+        f32x4 acc[6][2];
+#pragma unroll
+        for (int ct = 0; ct < 6; ++ct) acc[ct][0] = acc[ct][1] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        for (int q = q0; q < q1; q += 2) {
+            float4 fa[2][6], fb[2][2];
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+                if (q + j < q1) {
+                    fb[j][0] = frag_load(rs, boff, (q + j) * 2048);
+                    fb[j][1] = frag_load(rs, boff + 256, (q + j) * 2048);
+#pragma unroll
+                    for (int ct = 0; ct < 6; ++ct) fa[j][ct] = frag_load(ra, lane * 16, (ct * nq + q + j) * 1024);
+                }
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+                if (q + j < q1) {
+#pragma unroll
+                    for (int ct = 0; ct < 6; ++ct)
+#pragma unroll
+                        for (int hf = 0; hf < 2; ++hf) {
+                            acc[ct][hf] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[j][ct].x, fb[j][hf].x, acc[ct][hf], 0, 0, 0);
+                            acc[ct][hf] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[j][ct].y, fb[j][hf].y, acc[ct][hf], 0, 0, 0);
+                            acc[ct][hf] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[j][ct].z, fb[j][hf].z, acc[ct][hf], 0, 0, 0);
+                            acc[ct][hf] = __builtin_amdgcn_mfma_f32_16x16x4f32(fa[j][ct].w, fb[j][hf].w, acc[ct][hf], 0, 0, 0);
+                        }
+                }
+        }
+#pragma unroll
+        for (int ct = 0; ct < 6; ++ct)
+#pragma unroll
+            for (int hf = 0; hf < 2; ++hf)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) part[w][ct * 2 + hf][r][lane] = acc[ct][hf][r];
+        __syncthreads();
+        const int t = (int)(item / a.RB), rb = (int)(item % a.RB);
+        const float *ps = (const float *)(a.psave + item * 128);
+        const float *df = (const float *)(a.dfball + item * 64);
+        for (int idx = tid; idx < 32 * OPNET_KX; idx += 64 * DBOX_NW) {
+            const int clip = idx / OPNET_KX, col = idx - clip * OPNET_KX;
+            const int b = rb * 32 + clip;
+            if (b >= a.B) continue;
+            // D element (row = column of W_ih1 within its tile, clip) sits in lane clip + 16 (row >> 2), register row & 3
+            const int row = col & 15, l = (clip & 15) + 16 * (row >> 2), sl = (col >> 4) * 2 + (clip >> 4);
+            float v = part[0][sl][row & 3][l];
+#pragma unroll
+            for (int k = 1; k < DBOX_NW; ++k) v += part[k][sl][row & 3][l];
+            const int o = col / OPNET_FEATS_, f = col - o * OPNET_FEATS_;
+            v = fmaf(ps[((o >> 2) * 32 + clip) * 4 + (o & 3)], df[((f >> 2) * 32 + clip) * 4 + (f & 3)], v);
+            a.dboxes[((long)b * a.T + t) * OPNET_KX + col] = bad ? NAN : v;
+        }
+        if (item + gridDim.x < nitems) __syncthreads();
     }
 }
 
@@ -895,6 +1042,95 @@ __global__ void opnet_l1_final(const float *__restrict__ partial, int nblocks, f
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
     if (threadIdx.x == 0) *loss = (float)(s / (double)n);
+}
+
+// Cross-entropy on the selection logits [B][15][T] against a slot index per (b, t)
+// (torch.nn.functional.cross_entropy(logits, targets, ignore_index), mean over the targets that are not ignored) and its gradient
+// (softmax - onehot) / count.  Three launches: per-block partial sums of the loss and of the count (fixed tree), their sum in
+// fixed order (-> loss, 1 / count), the gradient with the softmax recomputed from the logits in registers.  A target outside
+// [0, 15) that is not ignore_index makes the loss NaN (torch raises there).  Nothing to average: loss 0, gradient 0.
+__device__ __forceinline__ long sel_ce_target(const void *tg, int is64, long i)
+{
+    return is64 ? (long)((const long long *)tg)[i] : (long)((const int *)tg)[i];
+}
+
+__global__ void __launch_bounds__(256) opnet_sel_ce_partial(const float *__restrict__ lg, const void *__restrict__ tg, int is64, long ignore,
+                                                            double *__restrict__ psum, unsigned *__restrict__ pcnt, int B, int T)
+{
+    __shared__ double red[256];
+    __shared__ unsigned redc[256];
+    const long n = (long)B * T;
+    double s = 0.0;
+    unsigned c = 0;
+    for (long i = blockIdx.x * 256L + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+        const long tgt = sel_ce_target(tg, is64, i);
+        if (tgt == ignore) continue;
+        ++c;
+        if (tgt < 0 || tgt >= OPNET_SLOTS_) { s += (double)NAN; continue; }
+        const long b = i / T;
+        const float *row = lg + b * OPNET_SLOTS_ * T + (i - b * T);
+        float l[OPNET_SLOTS_], m = -INFINITY, lt = 0.f;
+#pragma unroll
+        for (int o = 0; o < OPNET_SLOTS_; ++o) {
+            l[o] = row[(long)o * T];
+            m = fmaxf(m, l[o]);
+            if (o == (int)tgt) lt = l[o];
+        }
+        float se = 0.f;
+#pragma unroll
+        for (int o = 0; o < OPNET_SLOTS_; ++o) se += expf(l[o] - m);
+        s += ((double)m - (double)lt) + (double)logf(se);
+    }
+    red[threadIdx.x] = s;
+    redc[threadIdx.x] = c;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (threadIdx.x < o) { red[threadIdx.x] += red[threadIdx.x + o]; redc[threadIdx.x] += redc[threadIdx.x + o]; }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) { psum[blockIdx.x] = red[0]; pcnt[blockIdx.x] = redc[0]; }
+}
+
+__global__ void opnet_sel_ce_final(const double *__restrict__ psum, const unsigned *__restrict__ pcnt, int nblocks,
+                                   float *__restrict__ loss, float *__restrict__ inv_count)
+{
+    double s = 0.0;
+    unsigned long long c = 0;
+    for (int i = threadIdx.x; i < nblocks; i += 64) { s += psum[i]; c += pcnt[i]; }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { s += __shfl_xor(s, o); c += __shfl_xor(c, o); }
+    if (threadIdx.x == 0) {
+        *loss = c ? (float)(s / (double)c) : 0.f;
+        *inv_count = c ? (float)(1.0 / (double)c) : 0.f;
+    }
+}
+
+__global__ void __launch_bounds__(256) opnet_sel_ce_grad(const float *__restrict__ lg, const void *__restrict__ tg, int is64, long ignore,
+                                                         const float *__restrict__ inv_count, float *__restrict__ dlg, int B, int T)
+{
+    const long n = (long)B * T;
+    const float inv = *inv_count;
+    for (long i = blockIdx.x * 256L + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+        const long tgt = sel_ce_target(tg, is64, i);
+        const long b = i / T;
+        const long base = b * OPNET_SLOTS_ * T + (i - b * T);
+        if (tgt == ignore) {
+#pragma unroll
+            for (int o = 0; o < OPNET_SLOTS_; ++o) dlg[base + (long)o * T] = 0.f;
+            continue;
+        }
+        float l[OPNET_SLOTS_], m = -INFINITY;
+#pragma unroll
+        for (int o = 0; o < OPNET_SLOTS_; ++o) { l[o] = lg[base + (long)o * T]; m = fmaxf(m, l[o]); }
+        float se = 0.f;
+#pragma unroll
+        for (int o = 0; o < OPNET_SLOTS_; ++o) { l[o] = expf(l[o] - m); se += l[o]; }
+        const float r = 1.0f / se;
+        const bool valid = tgt >= 0 && tgt < OPNET_SLOTS_;
+#pragma unroll
+        for (int o = 0; o < OPNET_SLOTS_; ++o)
+            dlg[base + (long)o * T] = valid ? (l[o] * r - (o == (int)tgt ? 1.0f : 0.0f)) * inv : NAN;
+    }
 }
 
 // torch.optim.Adam.step (training_main.py:150,217): defaults betas (0.9, 0.999), eps 1e-8, no weight

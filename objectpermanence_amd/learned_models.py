@@ -74,12 +74,24 @@ def _stream_ptr(device: torch.device) -> int:
     return torch.cuda.current_stream(device).cuda_stream
 
 
+def _extra_grad_operands(ctx, grad_y, grad_logits, dev):
+    """the operands of a backward that may carry the opt-in extras: dy (zeros when the loss touches the logits only), the
+    upstream logit gradient [B,15,T] or None, and the output buffer of d boxes [B,T,15,6] when `boxes` wants a gradient"""
+    B, T = ctx.shape
+    grad_y = torch.zeros((B, T, 4), dtype=torch.float32, device=dev) if grad_y is None else grad_y.contiguous().float()
+    if grad_logits is not None:
+        grad_logits = grad_logits.contiguous().float()
+    dboxes = torch.empty((B, T, 15, 6), dtype=torch.float32, device=dev) if ctx.needs_input_grad[1] else None
+    return grad_y, grad_logits, dboxes
+
+
 class _OPNetTrainFunction(torch.autograd.Function):
     """Autograd bridge: forward = opnet_train_forward_f32 (keeps the history in the module's training
-    workspace), backward = opnet_train_backward_f32 (BPTT + weight-gradient GEMMs)."""
+    workspace), backward = opnet_train_backward_f32 (BPTT + weight-gradient GEMMs) - or opnet_train_backward_ex_f32 when a
+    gradient arrives through the logits (logits_grad=True) or `boxes` wants one."""
 
     @staticmethod
-    def forward(ctx, module, boxes, *weights):
+    def forward(ctx, module, boxes, logits_grad, *weights):
         lib = _lib.load()
         B, T = int(boxes.shape[0]), int(boxes.shape[1])
         dev = boxes.device
@@ -98,7 +110,8 @@ class _OPNetTrainFunction(torch.autograd.Function):
         module._train_gen += 1
         ctx.module, ctx.gen, ctx.shape = module, module._train_gen, (B, T)
         ctx.wshapes = [tuple(w.shape) for w in weights]
-        ctx.mark_non_differentiable(logits)
+        if not logits_grad:
+            ctx.mark_non_differentiable(logits)
         ctx.set_materialize_grads(False)
         return y, logits
 
@@ -108,13 +121,13 @@ class _OPNetTrainFunction(torch.autograd.Function):
         if ctx.gen != module._train_gen:
             raise RuntimeError("OPNet: backward() after another training forward - the saved history of this "
                                "forward has been overwritten (one history per module)")
-        n_in = 2 + len(ctx.wshapes)
-        if grad_y is None:
+        n_in = 3 + len(ctx.wshapes)
+        if grad_y is None and grad_logits is None:
             return (None,) * n_in
         lib = _lib.load()
         B, T = ctx.shape
-        dev = grad_y.device
-        grad_y = grad_y.contiguous().float()
+        dev = (grad_y if grad_y is not None else grad_logits).device
+        grad_y, grad_logits, dboxes = _extra_grad_operands(ctx, grad_y, grad_logits, dev)
         # with a gradient bucket on the module (data-parallel training, parallel.GradBucket) the six weight gradients are
         # written straight into its flat buffer: the all-reduce then needs no gather copy
         # - but only while no parameter holds a gradient: a p.grad that is still set (zero_grad(set_to_none=False), gradient
@@ -129,22 +142,30 @@ class _OPNetTrainFunction(torch.autograd.Function):
             grads = [torch.empty(s, dtype=torch.float32, device=dev) for s in ctx.wshapes]
         tb = module._train
         with torch.cuda.device(dev):
-            rc = lib.opnet_train_backward_f32(grad_y.data_ptr(), tb.image.data_ptr(), tb.history.data_ptr(), tb.history.numel(),
-                                              *(g.data_ptr() for g in grads), B, T, module._h1, module._h2, _stream_ptr(dev))
+            if grad_logits is None and dboxes is None:
+                rc = lib.opnet_train_backward_f32(grad_y.data_ptr(), tb.image.data_ptr(), tb.history.data_ptr(), tb.history.numel(),
+                                                  *(g.data_ptr() for g in grads), B, T, module._h1, module._h2, _stream_ptr(dev))
+            else:
+                extra = tb.extra_for(B, T, dev, (lib.opnet_train_extra_workspace_bytes, B, T, module._h1, module._h2))
+                rc = lib.opnet_train_backward_ex_f32(grad_y.data_ptr(), tb.image.data_ptr(), tb.history.data_ptr(), tb.history.numel(),
+                                                     *(g.data_ptr() for g in grads), B, T, module._h1, module._h2,
+                                                     None if grad_logits is None else grad_logits.data_ptr(),
+                                                     None if dboxes is None else dboxes.data_ptr(),
+                                                     extra.data_ptr(), extra.numel(), _stream_ptr(dev))
         _lib.check(rc, "opnet_train_backward_f32")
         # the abort words of the step's two persistent launches (sticky from the forward): mirrored to the host behind the
         # backward; training.finish_step / OPNet.training_step_aborted() look at them at the caller's next sync point
         off = lib.opnet_train_status_offset(B, T, module._h1, module._h2)
         if off != _lib.NO_OFFSET and lib.opnet_xcd4_enabled():
             module._monitor.watch(tb.history, off, module._note_training_abort, "opnet_xcd4_forward/backward (training step)")
-        return (None, None) + tuple(grads)
+        return (None, dboxes, None) + tuple(grads)
 
 
 class _OPNetMlpTrainFunction(torch.autograd.Function):
     """OPNetLstmMlp training: the OPNet history/BPTT machinery with relu(hidden_layer) in the video role."""
 
     @staticmethod
-    def forward(ctx, module, boxes, *weights):
+    def forward(ctx, module, boxes, logits_grad, *weights):
         lib = _lib.load()
         B, T = int(boxes.shape[0]), int(boxes.shape[1])
         dev = boxes.device
@@ -164,7 +185,8 @@ class _OPNetMlpTrainFunction(torch.autograd.Function):
         module._train_gen += 1
         ctx.module, ctx.gen, ctx.shape = module, module._train_gen, (B, T)
         ctx.wshapes = [tuple(w.shape) for w in weights]
-        ctx.mark_non_differentiable(logits)
+        if not logits_grad:
+            ctx.mark_non_differentiable(logits)
         ctx.set_materialize_grads(False)
         return y, logits
 
@@ -174,27 +196,40 @@ class _OPNetMlpTrainFunction(torch.autograd.Function):
         if ctx.gen != module._train_gen:
             raise RuntimeError("OPNetLstmMlp: backward() after another training forward - the saved history of "
                                "this forward has been overwritten (one history per module)")
-        n_in = 2 + len(ctx.wshapes)
-        if grad_y is None:
+        n_in = 3 + len(ctx.wshapes)
+        if grad_y is None and grad_logits is None:
             return (None,) * n_in
         lib = _lib.load()
         B, T = ctx.shape
-        dev = grad_y.device
-        grad_y = grad_y.contiguous().float()
+        dev = (grad_y if grad_y is not None else grad_logits).device
+        grad_y, grad_logits, dboxes = _extra_grad_operands(ctx, grad_y, grad_logits, dev)
         g_ih1, g_hh1, g_sel, _, g_out = [torch.empty(s, dtype=torch.float32, device=dev) for s in ctx.wshapes]
         g_hid4 = torch.empty((4 * module._h2, 6), dtype=torch.float32, device=dev)
+        tb = module._train
         with torch.cuda.device(dev):
-            rc = lib.opnet_mlp_train_backward_f32(grad_y.data_ptr(), module._train.image.data_ptr(),
-                                                  module._train.history.data_ptr(), module._train.history.numel(), g_ih1.data_ptr(),
-                                                  g_hh1.data_ptr(), g_sel.data_ptr(), g_hid4.data_ptr(),
-                                                  g_out.data_ptr(), B, T, module._h1, module._h2, _stream_ptr(dev))
+            if grad_logits is None and dboxes is None:
+                rc = lib.opnet_mlp_train_backward_f32(grad_y.data_ptr(), tb.image.data_ptr(), tb.history.data_ptr(), tb.history.numel(),
+                                                      g_ih1.data_ptr(), g_hh1.data_ptr(), g_sel.data_ptr(), g_hid4.data_ptr(),
+                                                      g_out.data_ptr(), B, T, module._h1, module._h2, _stream_ptr(dev))
+            else:
+                extra = tb.extra_for(B, T, dev, (lib.opnet_train_extra_workspace_bytes, B, T, module._h1, module._h2))
+                rc = lib.opnet_mlp_train_backward_ex_f32(grad_y.data_ptr(), tb.image.data_ptr(), tb.history.data_ptr(),
+                                                         tb.history.numel(), g_ih1.data_ptr(), g_hh1.data_ptr(), g_sel.data_ptr(),
+                                                         g_hid4.data_ptr(), g_out.data_ptr(), B, T, module._h1, module._h2,
+                                                         None if grad_logits is None else grad_logits.data_ptr(),
+                                                         None if dboxes is None else dboxes.data_ptr(),
+                                                         extra.data_ptr(), extra.numel(), _stream_ptr(dev))
         _lib.check(rc, "opnet_mlp_train_backward_f32")
-        return (None, None, g_ih1, g_hh1, g_sel, g_hid4[:module._h2].contiguous(), g_out)
+        return (None, dboxes, None, g_ih1, g_hh1, g_sel, g_hid4[:module._h2].contiguous(), g_out)
 
 
 class OPNet(AbstractCaterModel):
     """reference learned_models.py:18-52.  forward(boxes [B,T,15,6]) -> (y_boxes [B,T,4],
-    object_to_track_prediction [B,15,T])."""
+    object_to_track_prediction [B,15,T]).
+
+    Training: the logits come back non-differentiable unless the forward is called with logits_grad=True (a loss on the
+    selection, e.g. optim.selection_cross_entropy); `boxes` gets a gradient when it requires one.  Either runs the reverse
+    recurrence on the launch chain."""
 
     def __init__(self, config: Dict[str, int]):
         super().__init__(config)
@@ -384,7 +419,7 @@ class OPNet(AbstractCaterModel):
         return {k: ws[:12].view(torch.int32).tolist() for k, ws in self._xws.items()}
 
     # -- forward ------------------------------------------------------------------------------
-    def forward(self, boxes: torch.Tensor):
+    def forward(self, boxes: torch.Tensor, logits_grad: bool = False):
         if not boxes.is_cuda:
             raise RuntimeError("objectpermanence_amd.OPNet runs on MI355X only: move `boxes` (and the model) "
                                "to a ROCm device; there is no CPU fallback")
@@ -392,10 +427,10 @@ class OPNet(AbstractCaterModel):
             raise ValueError(f"boxes must be [B, T, 15, 6], got {tuple(boxes.shape)}")
         lib = _lib.load()
         boxes = boxes.contiguous().float()
-        if torch.is_grad_enabled() and any(w.requires_grad for w in self._weights()):
+        if torch.is_grad_enabled() and (boxes.requires_grad or any(w.requires_grad for w in self._weights())):
             ws = self._weights()
             check_weights(ws, boxes.device, "OPNet")
-            return _OPNetTrainFunction.apply(self, boxes, *ws)
+            return _OPNetTrainFunction.apply(self, boxes, bool(logits_grad), *ws)
         B, T = int(boxes.shape[0]), int(boxes.shape[1])
         dev = boxes.device
         with torch.cuda.device(dev):
@@ -1059,15 +1094,16 @@ class OPNetLstmMlp(AbstractCaterModel):
                                     *(w.data_ptr() for w in ws_list), buf.data_ptr(), n, self._h1, self._h2, stream),
                                     "opnet_mlp_pack_weights_f32"), zero=True)
 
-    def forward(self, boxes: torch.Tensor):
+    def forward(self, boxes: torch.Tensor, logits_grad: bool = False):
+        """logits_grad / boxes.requires_grad: as for OPNet"""
         _check_input(self, boxes, 6)
         lib = _lib.load()
         boxes = boxes.contiguous().float()
         B, T, dev = int(boxes.shape[0]), int(boxes.shape[1]), boxes.device
-        if _wants_grad(self):
+        if _wants_grad(self) or (torch.is_grad_enabled() and boxes.requires_grad):
             ws_list = self._weights()
             check_weights(ws_list, dev, "OPNetLstmMlp")
-            return _OPNetMlpTrainFunction.apply(self, boxes, *ws_list)
+            return _OPNetMlpTrainFunction.apply(self, boxes, bool(logits_grad), *ws_list)
         with torch.cuda.device(dev):
             stream = _stream_ptr(dev)
             packed = self._packed_weights(dev)

@@ -2,6 +2,9 @@
 
 * ``l1_mean(y, labels)``  == ``torch.mean(nn.L1Loss(reduction="none")(y, labels))``
   (reference baselines/training_main.py:152,192,204) - one fused forward+backward kernel pair.
+* ``selection_cross_entropy(logits, targets)`` == ``F.cross_entropy(logits, targets, ignore_index=-100)`` on the
+  selection logits [B,15,T] of OPNet / OPNetLstmMlp (which the reference permutes "for CE loss",
+  learned_models.py:49-50) - one HIP call for value and gradient.
 * ``FusedAdam``           == ``torch.optim.Adam(params, lr)`` with the reference's defaults
   (training_main.py:150): betas (0.9, 0.999), eps 1e-8, no weight decay.  It is a
   ``torch.optim.Optimizer`` so ``ReduceLROnPlateau`` (training_main.py:151,247) drives it unchanged.
@@ -77,6 +80,53 @@ def smooth_l1_mean(y: torch.Tensor, labels: torch.Tensor, beta: float = 1.0) -> 
     """torch.nn.SmoothL1Loss(beta=beta)(y, labels) - the loss BASELINE.json's config 2 names (the reference
     trains with L1; this is the extra knob SURVEY.md section 0 asks for)."""
     return _L1Mean.apply(y, labels, float(beta))
+
+
+def selection_loss_and_grad(logits: torch.Tensor, targets: torch.Tensor, ignore_index: int = -100):
+    """(loss, dloss/dlogits) of the mean cross-entropy of the selection logits [B,15,T] against targets [B,T] (int32 or int64
+    slot indices; ignore_index entries do not count) WITHOUT an autograd node - see loss_and_grad.  One call of
+    opnet_selection_ce_f32: fixed-order reduction (the same bits every run), all targets ignored gives loss 0 / gradient 0."""
+    if not logits.is_cuda:
+        raise RuntimeError("selection_cross_entropy runs on the GPU only (no CPU fallback)")
+    if logits.dim() != 3 or logits.shape[1] != 15:
+        raise ValueError(f"logits must be [B, 15, T], got {tuple(logits.shape)}")
+    B, T = int(logits.shape[0]), int(logits.shape[2])
+    if tuple(targets.shape) != (B, T):
+        raise ValueError(f"targets must be [B, T] = [{B}, {T}], got {tuple(targets.shape)}")
+    if targets.dtype not in (torch.int32, torch.int64):
+        raise TypeError(f"targets must be int32 or int64, got {targets.dtype}")
+    lib = _lib.load()
+    lg = logits.detach().contiguous().float()
+    tg = targets.to(lg.device).contiguous()
+    loss = torch.empty((), dtype=torch.float32, device=lg.device)
+    dlg = torch.empty_like(lg)
+    scratch = torch.empty(16384, dtype=torch.uint8, device=lg.device)
+    with torch.cuda.device(lg.device):
+        rc = lib.opnet_selection_ce_f32(lg.data_ptr(), tg.data_ptr(), int(tg.dtype == torch.int64), int(ignore_index), loss.data_ptr(),
+                                        dlg.data_ptr(), B, T, scratch.data_ptr(), scratch.numel(),
+                                        torch.cuda.current_stream(lg.device).cuda_stream)
+    _lib.check(rc, "opnet_selection_ce_f32")
+    return loss, dlg
+
+
+class _SelectionCE(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, targets, ignore_index):
+        loss, dlg = selection_loss_and_grad(logits, targets, ignore_index)
+        ctx.save_for_backward(dlg)
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        (dlg,) = ctx.saved_tensors
+        return dlg * grad_out, None, None
+
+
+def selection_cross_entropy(logits: torch.Tensor, targets: torch.Tensor, ignore_index: int = -100) -> torch.Tensor:
+    """torch.nn.functional.cross_entropy(logits [B,15,T], targets [B,T], ignore_index=ignore_index): which slot the model
+    should look at in each frame.  The logits must come from a forward with logits_grad=True for the loss to reach the
+    weights."""
+    return _SelectionCE.apply(logits, targets, int(ignore_index))
 
 
 class FusedAdam(torch.optim.Optimizer):

@@ -19,7 +19,7 @@ import torch
 import torch.distributed as dist
 
 from . import parallel
-from .optim import l1_mean, loss_and_grad, smooth_l1_mean
+from .optim import l1_mean, loss_and_grad, selection_loss_and_grad, smooth_l1_mean
 from .supported_models import DOUBLE_OUTPUT_MODELS, NO_LABELS_MODELS
 
 
@@ -45,8 +45,13 @@ def compute_loss(model_name: str, output: torch.Tensor, labels: torch.Tensor, ma
 def train_step(model_name: str, model: torch.nn.Module, optimizer: torch.optim.Optimizer, boxes: Optional[torch.Tensor],
                labels: Optional[torch.Tensor], mask: Optional[torch.Tensor] = None, group: Optional[dist.ProcessGroup] = None,
                n_global: Optional[int] = None, comm_stream: Optional[torch.cuda.Stream] = None,
-               loss_kind: str = "l1", overlap=None, comm_events: Optional[list] = None) -> torch.Tensor:
+               loss_kind: str = "l1", overlap=None, comm_events: Optional[list] = None,
+               selection_targets: Optional[torch.Tensor] = None, selection_weight: float = 1.0) -> torch.Tensor:
     """zero_grad -> forward -> loss -> backward -> [gradient all-reduce] -> Adam (training_main.py:183-217).
+
+    selection_targets [B, T] (int32 / int64 slot indices, -100 = no label; the double-output models only): supervises the
+    selection head as well - loss = prediction loss + selection_weight * cross-entropy(logits, selection_targets), the
+    backward started from both outputs at once.
 
     Data parallel: EVERY rank calls this for every global batch - a rank whose slice of the batch is empty passes
     boxes=None, contributes zero gradients with weight 0 / n_global and still joins the collective and the optimiser step
@@ -55,6 +60,8 @@ def train_step(model_name: str, model: torch.nn.Module, optimizer: torch.optim.O
     `comm_stream` as soon as the backward (its last kernel is the merged weight-gradient GEMM) is enqueued, `overlap()` -
     the caller's work that does not depend on the new weights: the next batch's host-to-device copies, its input packing -
     runs on the current stream meanwhile, and only then does the current stream wait for the collective and run Adam."""
+    if selection_targets is not None and model_name not in DOUBLE_OUTPUT_MODELS:
+        raise ValueError(f"selection_targets: {model_name} has no selection logits")
     distributed = parallel.is_active(group)       # > 1 rank, or a forced group of one (OPNET_FORCE_DIST=1: the GPU tests)
     bucket = getattr(model, "_grad_bucket", None)
     if bucket is None:
@@ -62,7 +69,19 @@ def train_step(model_name: str, model: torch.nn.Module, optimizer: torch.optim.O
     optimizer.zero_grad(set_to_none=True)
     n_local = 0 if boxes is None else int(boxes.shape[0])
     guard_word = None
-    if n_local > 0:
+    if n_local > 0 and selection_targets is not None:
+        output, logits = model(boxes, logits_grad=True)
+        if model_name in NO_LABELS_MODELS:
+            pred, _, _ = compute_loss(model_name, output, labels, mask, loss_kind, with_consistency=False)
+            (dy,) = torch.autograd.grad(pred, output, retain_graph=False)
+            pred = pred.detach()
+        else:
+            pred, dy = loss_and_grad(output, labels, 1.0 if loss_kind == "smooth_l1" else 0.0)
+        ce, dlg = selection_loss_and_grad(logits, selection_targets)
+        loss = pred + float(selection_weight) * ce
+        torch.autograd.backward([output, logits], [dy, dlg * float(selection_weight)])
+        guard_word = model.launch_guard() if hasattr(model, "launch_guard") else None
+    elif n_local > 0:
         out = model(boxes)
         output = out[0] if model_name in DOUBLE_OUTPUT_MODELS else out
         if model_name not in NO_LABELS_MODELS and output.is_cuda:
