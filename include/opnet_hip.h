@@ -276,6 +276,27 @@ int opnet_mlp_train_backward_ex_f32(const float *dy, const float *packed, void *
                                     int B, int T, int H1, int H2, const float *dlogits, float *dboxes, void *extra,
                                     size_t extra_bytes, void *stream);
 
+/* ---- training from a carried state: truncated BPTT ----------------------------------------------
+ * The training step of OPNet (mlp = 0) or OPNetLstmMlp (mlp = 1) with an initial LSTM state instead of h0 = c0 = 0 and the
+ * final state returned.  State and state gradients are rows [B][opnet_stream_state_floats(H1, H2)] = [h1 | c1 | h2 | c2] in
+ * torch's unit order - the stream pool's row layout, so a slice of a pool can be passed as it lies; 16-byte aligned device
+ * memory.  OPNetLstmMlp has no video LSTM: its h2 / c2 columns are neither read nor written.
+ *   state_in   in:  the state before frame 0 (NULL: zero)          state_out  out: the state after frame T-1 (NULL: not wanted)
+ *   dstate_seed in: the gradient arriving on state_out (NULL: none) dstate_in  out: the gradient of state_in (NULL: not wanted)
+ * Packed image, workspace, sizes and every other argument as the opnet_train_* / opnet_mlp_train_* entry points of the model
+ * (g_ih2 is g_hidden_scratch and g_hh2 is ignored when mlp = 1); dlogits / dboxes / extra as opnet_train_backward_ex_f32 (all
+ * may be NULL).  Both calls run on the launch chain at every batch size - the persistent training launches carry no state -
+ * with plain fp32 copies at the boundaries: a clip's frames see the arithmetic of the whole-clip chain whatever the chunking,
+ * and with state_in = dstate_seed = NULL the step computes what the launch chain's plain step computes.  The backward must
+ * follow the forward of the same step (one history per workspace). */
+int opnet_train_forward_state_f32(const float *boxes, const float *packed, float *y, float *logits, void *workspace,
+                                  size_t workspace_bytes, int B, int T, int H1, int H2, int mlp, const float *state_in,
+                                  float *state_out, void *stream);
+int opnet_train_backward_state_f32(const float *dy, const float *packed, void *workspace, size_t workspace_bytes,
+                                   float *g_ih1, float *g_hh1, float *g_sel, float *g_ih2, float *g_hh2, float *g_out,
+                                   int B, int T, int H1, int H2, int mlp, const float *dlogits, float *dboxes, void *extra,
+                                   size_t extra_bytes, const float *dstate_seed, float *dstate_in, void *stream);
+
 /* ---- stateful streams: OPNet / OPNetLstmMlp with the LSTM state carried across calls ---------------------
  * A call advances n streams by k >= 1 frames each.  A stream's state is a row of the caller-owned pool
  *   state [capacity][opnet_stream_state_floats(H1, H2)] = [h1 | c1 | h2 | c2]   (torch nn.LSTM unit order)

@@ -147,6 +147,12 @@ def _declare(lib):
     lib.opnet_mlp_train_backward_ex_f32.restype = c_int
     lib.opnet_mlp_train_backward_ex_f32.argtypes = lib.opnet_mlp_train_backward_f32.argtypes[:-1] + [fp, fp, c_void_p, c_size_t,
                                                                                                      c_void_p]
+    lib.opnet_train_forward_state_f32.restype = c_int
+    lib.opnet_train_forward_state_f32.argtypes = [fp, fp, fp, fp, c_void_p, c_size_t, c_int, c_int, c_int, c_int, c_int, fp, fp,
+                                                  c_void_p]
+    lib.opnet_train_backward_state_f32.restype = c_int
+    lib.opnet_train_backward_state_f32.argtypes = [fp, fp, c_void_p, c_size_t, fp, fp, fp, fp, fp, fp, c_int, c_int, c_int, c_int,
+                                                   c_int, fp, fp, c_void_p, c_size_t, fp, fp, c_void_p]
     lib.opseq_lstm_stack_packed_bytes.restype = c_size_t
     lib.opseq_lstm_stack_packed_bytes.argtypes = [c_int, c_int, c_int]
     lib.opseq_lstm_stack_workspace_bytes.restype = c_size_t
@@ -364,7 +370,7 @@ EXPORTS = [
     "opnet_stream_step_x4_f32",
     "opnet_online_encode_f32", "opnet_online_encode_ragged_f32",
     "opnet_mlp_train_pack_weights_f32", "opnet_mlp_train_forward_f32", "opnet_mlp_train_backward_f32",
-    "opnet_mlp_train_backward_ex_f32",
+    "opnet_mlp_train_backward_ex_f32", "opnet_train_forward_state_f32", "opnet_train_backward_state_f32",
     "opseq_lstm_stack_packed_bytes", "opseq_lstm_stack_workspace_bytes", "opseq_lstm_stack_pack_weights_f32",
     "opseq_lstm_stack_forward_f32", "opseq_lstm_stack_forward_graph_f32", "opseq_graph_cache_clear",
     "opseq_stream_state_floats", "opseq_stream_workspace_bytes", "opseq_stream_step_f32", "opseq_stream_step_ragged_f32",

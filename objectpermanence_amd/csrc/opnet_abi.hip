@@ -3,6 +3,7 @@
 #include "opnet_kernels.hip"
 #include "opnet_xcd_kernels.hip"
 #include "opnet_train_kernels.hip"
+#include "opnet_state_train_kernels.hip"
 #include "opnet_xcd4_kernels.hip"
 #include "seq_kernels.hip"
 #include "seq_xcd_kernels.hip"
@@ -1428,6 +1429,10 @@ struct TrainExtras {
     float *dboxes;          // [B][T][15][6] out: gradient of the input boxes
     void *extra;            // the caller's second workspace (extra_workspace_layout)
     size_t extra_bytes;
+    // a step from a carried state (opnet_train_backward_state_f32): rows [B][2*H1 + 2*H2] = [h1 | c1 | h2 | c2]
+    int stateful;               // the step's forward was opnet_train_forward_state_f32: the reverse recurrence runs on the launch chain
+    const float *dstate_seed;   // in:  gradient arriving on the final state (null: none)
+    float *dstate_in;           // out: gradient of the initial state (null: not wanted)
 };
 
 static int train_backward_impl(const float *dy, const float *packed, void *workspace, size_t workspace_bytes,
@@ -1460,7 +1465,7 @@ extern "C" int opnet_train_backward_ex_f32(const float *dy, const float *packed,
                                            size_t extra_bytes, void *stream)
 {
     if (!g_hh2) return fail(OPNET_EINVAL, "null pointer");
-    const TrainExtras ex{dlogits, dboxes, extra, extra_bytes};
+    const TrainExtras ex{dlogits, dboxes, extra, extra_bytes, 0, nullptr, nullptr};
     return train_backward_impl(dy, packed, workspace, workspace_bytes, g_ih1, g_hh1, g_sel, g_ih2, g_hh2, g_out, B, T,
                                H1, H2, stream, 0, &ex);
 }
@@ -1470,7 +1475,7 @@ extern "C" int opnet_mlp_train_backward_ex_f32(const float *dy, const float *pac
                                                int B, int T, int H1, int H2, const float *dlogits, float *dboxes, void *extra,
                                                size_t extra_bytes, void *stream)
 {
-    const TrainExtras ex{dlogits, dboxes, extra, extra_bytes};
+    const TrainExtras ex{dlogits, dboxes, extra, extra_bytes, 0, nullptr, nullptr};
     return train_backward_impl(dy, packed, workspace, workspace_bytes, g_ih1, g_hh1, g_sel, g_hidden_scratch, nullptr,
                                g_out, B, T, H1, H2, stream, 1, &ex);
 }
@@ -1513,6 +1518,9 @@ static int train_backward_impl(const float *dy, const float *packed, void *works
         if (ex->dlogits) bw.dlin = (const float4 *)((char *)ex->extra + E.dlin);
         if (ex->dboxes) bw.dfball = (float4 *)((char *)ex->extra + E.dfball);
     }
+    const bool stateful = ex && ex->stateful;
+    if (stateful && ((ex->dstate_seed && !aligned16(ex->dstate_seed)) || (ex->dstate_in && !aligned16(ex->dstate_in))))
+        return fail(OPNET_EINVAL, "dstate_seed / dstate_in must be 16-byte aligned");
     const TrainWorkspaceLayout W = train_workspace_layout(B, T, H1, H2);
     hipStream_t st = (hipStream_t)stream;
     const int RB = a.RB;
@@ -1521,13 +1529,18 @@ static int train_backward_impl(const float *dy, const float *packed, void *works
     // two chains of fused steps below - not adopted)
     // (a step with extras runs the launch chain: the persistent reverse recurrence neither takes a logit gradient nor keeps
     // d frames_boxes - the route of a 33 .. 96-clip step, whose forward is the 4-clip persistent launch too)
-    const bool x4_bwd = !mlp && !extras && x4_use(B, T, H1, H2) && env_int("OPNET_XCD4_BWD", 1) != 0;
+    // (... and so does a step from a carried state: the persistent reverse recurrence takes no seed and leaves no d state)
+    const bool x4_bwd = !mlp && !extras && !stateful && x4_use(B, T, H1, H2) && env_int("OPNET_XCD4_BWD", 1) != 0;
     if (extras && ex->dlogits)
         opnet_pack_dlogits<<<256, 256, 0, st>>>(ex->dlogits, (float4 *)((char *)ex->extra + E.dlin), B, T, RB);
     if (!x4_bwd)        // (the 4-clip persistent form packs dy in its own initialisation launch)
         opnet_pack_dy<<<256, 256, 0, st>>>((const float4 *)dy, (float4 *)(w + W.dyp), (float *)(w + W.dcz),
                                             (long)((W.dcz_end - W.dcz) / 4), B, T, RB);
     bw.mlp = mlp;
+    if (stateful && ex->dstate_seed) {      // behind opnet_pack_dy, which zeroed the carries
+        bw.seeded = 1;
+        opnet_pack_dstate_seed<<<ew_blocks((long)RB * (H1 + H2) * 32, 256), 256, 0, st>>>(bw, ex->dstate_seed);
+    }
     if (mlp) opnet_mlp_dhid<<<4096, 256, 0, st>>>(bw);
     // Reverse recurrence.  Up to four row blocks: ONE fused launch per step - a workgroup owns complete dh rows, so the
     // cell backward rides the product's epilogue.  Larger batches: the split-K pair (4x the workgroups per product,
@@ -1598,6 +1611,9 @@ static int train_backward_impl(const float *dy, const float *packed, void *works
             if (n < T) opnet_bwd_gemm<<<ggemm, OPNET_THREADS, 0, st>>>(bw, n);
         }
     }
+    // d state_in = (W_hh^T da_0, the carry after t = 0), one launch behind every form of the chain
+    if (stateful && ex->dstate_in)
+        opnet_bwd_dstate<<<dim3(2 * (H2 / 16 + H1 / 16), RB < OPNET_MAX_GY ? RB : OPNET_MAX_GY, 1), FUSED_THREADS, 0, st>>>(bw, ex->dstate_in);
     // weight gradients over the saved histories
     WgradBatch wb;
     int njobs = 0, ntiles = 0;
@@ -1710,6 +1726,53 @@ extern "C" int opnet_mlp_train_forward_f32(const float *boxes, const float *pack
     opnet_copy_out<<<copy_grid(B, T), 256, 0, st>>>(dio);
     HIP_TRY(hipGetLastError());
     return OPNET_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// training from a carried state: the launch chain's forward with slot 0 of the histories gathered from
+// the caller's rows and slot T gathered back; the backward is train_backward_impl with TrainExtras::stateful
+// ------------------------------------------------------------------------------------------------
+extern "C" int opnet_train_forward_state_f32(const float *boxes, const float *packed, float *y, float *logits, void *workspace,
+                                             size_t workspace_bytes, int B, int T, int H1, int H2, int mlp,
+                                             const float *state_in, float *state_out, void *stream)
+{
+    StepArgs a; OpnetIO io; BwdArgs bw;
+    if (!boxes || !y || !logits) return fail(OPNET_EINVAL, "null pointer");
+    if (!aligned16(y) || (((uintptr_t)boxes) & 7u)) return fail(OPNET_EINVAL, "y must be 16-byte and boxes 8-byte aligned");
+    if (!aligned16(state_in) || !aligned16(state_out)) return fail(OPNET_EINVAL, "state_in / state_out must be 16-byte aligned");
+    if (int rc = make_train_args(&a, &io, &bw, boxes, packed, y, logits, workspace, workspace_bytes, B, T, H1, H2))
+        return rc;
+    a.mlp = mlp ? 1 : 0;
+    const TrainWorkspaceLayout W = train_workspace_layout(B, T, H1, H2);
+    hipStream_t st = (hipStream_t)stream;
+    OpnetIO *dio = (OpnetIO *)((char *)workspace + W.io);
+    opnet_set_io<<<1, 1, 0, st>>>(dio, io);
+    opnet_pack_input<<<dim3(T, a.RB), 256, 0, st>>>(dio);      // (zeroes the histories: a null state_in is the zero state)
+    const unsigned nb = ew_blocks((long)a.RB * ((H1 + H2) / 4) * 32, 256);
+    if (state_in) opnet_train_state_copy<false><<<nb, 256, 0, st>>>(a, (float *)state_in, 0);
+    if (!mlp)       // (the mlp image is always packed eagerly)
+        if (int rc = train_chain_layouts(packed, st)) return rc;
+    // (see opnet_train_forward_f32: a forward on the launch chain has to say "nothing aborted" itself)
+    if (train_status_offset(W, B, T, H1, H2) != (size_t)-1) HIP_TRY(hipMemsetAsync((char *)workspace + train_status_offset(W, B, T, H1, H2), 0, 32, st));
+    const dim3 grid = step_grid(a);
+    const opnet_step_fn stepk = step_kernel(a);
+    for (int s = 0; s < T + 3; ++s) stepk<<<grid, step_threads(a), 0, st>>>(a, s);
+    opnet_copy_out<<<copy_grid(B, T), 256, 0, st>>>(dio);
+    if (state_out) opnet_train_state_copy<true><<<nb, 256, 0, st>>>(a, state_out, T);
+    HIP_TRY(hipGetLastError());
+    return OPNET_OK;
+}
+
+extern "C" int opnet_train_backward_state_f32(const float *dy, const float *packed, void *workspace, size_t workspace_bytes,
+                                              float *g_ih1, float *g_hh1, float *g_sel, float *g_ih2, float *g_hh2, float *g_out,
+                                              int B, int T, int H1, int H2, int mlp, const float *dlogits, float *dboxes,
+                                              void *extra, size_t extra_bytes, const float *dstate_seed, float *dstate_in,
+                                              void *stream)
+{
+    if (!mlp && !g_hh2) return fail(OPNET_EINVAL, "null pointer");
+    const TrainExtras ex{dlogits, dboxes, extra, extra_bytes, 1, dstate_seed, dstate_in};
+    return train_backward_impl(dy, packed, workspace, workspace_bytes, g_ih1, g_hh1, g_sel, g_ih2, mlp ? nullptr : g_hh2, g_out,
+                               B, T, H1, H2, stream, mlp ? 1 : 0, &ex);
 }
 
 static int l1_family(const float *y, const float *labels, float *loss, float *dy, long n, void *scratch,

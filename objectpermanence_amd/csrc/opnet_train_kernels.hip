@@ -52,6 +52,10 @@ struct BwdArgs {
     // opt-in extras (null = off: the plain step): gradients through the selection logits and to the input boxes
     const float4 *dlin;     // [T][RB][4][32]  upstream gradient of the selection logits, packed like dlall - added to dl_t
     float4 *dfball;         // [T][RB][2][32]  d frames_boxes_t = W_ih2^T da2_t kept per step, in x2all's layout (6 of 8 floats written)
+    // opt-in (0 = off: the plain step): a gradient arrives on the final state.  The step t = T-1 then reads what every other step
+    // reads - dh from t + 1 out of dhpart (the seed sits in partial 0, zeros in the others), dc out of the carry - where
+    // opnet_pack_dstate_seed put them (opnet_state_train_kernels.hip)
+    int seeded;
 };
 
 // ------------------------------------------------------------------------------------------------
@@ -224,7 +228,7 @@ __global__ void __launch_bounds__(256) opnet_bwd_cell(const BwdArgs a, const int
         dh = fmaf(a.wout[2 * H2 + u], dy.z, dh);
         dh = fmaf(a.wout[3 * H2 + u], dy.w, dh);
         float dcc = 0.f;
-        if (t < T - 1) {
+        if (t < T - 1 || a.seeded) {
             const long ps = (long)a.RB * H2 * 32;
             dh += ((a.dhpart2[e] + a.dhpart2[ps + e]) + a.dhpart2[2 * ps + e]) + a.dhpart2[3 * ps + e];
             dcc = a.dc2[e];
@@ -301,7 +305,7 @@ __global__ void __launch_bounds__(256) opnet_bwd_cell(const BwdArgs a, const int
 #pragma unroll
         for (int o = 0; o < OPNET_SLOTS_; ++o) dh = fmaf(a.wsel[o * H1 + u], dl_s[clip][o], dh);
         float dcc = 0.f;
-        if (t < T - 1) {
+        if (t < T - 1 || a.seeded) {
             const long ps = (long)a.RB * H1 * 32;
             dh += ((a.dhpart1[e] + a.dhpart1[ps + e]) + a.dhpart1[2 * ps + e]) + a.dhpart1[3 * ps + e];
             dcc = a.dc1[e];
@@ -460,7 +464,7 @@ __global__ void __launch_bounds__(FUSED_THREADS) opnet_bwd_fused(const BwdArgs a
             if (owner) {
                 dy = a.dyp[((long)t * a.RB + rb) * 32 + clip];
                 wo0 = a.wout[u]; wo1 = a.wout[H2 + u]; wo2 = a.wout[2 * H2 + u]; wo3 = a.wout[3 * H2 + u];
-                if (t < T - 1) dcc = a.dc2[e];
+                if (t < T - 1 || a.seeded) dcc = a.dc2[e];
                 gs = a.g2[ge];
                 c_t = a.c2all[(((long)(t + 1)) * a.RB + rb) * H2 * 32 + (long)u * 32 + clip];
                 c_p = a.c2all[((long)t * a.RB + rb) * H2 * 32 + (long)u * 32 + clip];
@@ -469,6 +473,8 @@ __global__ void __launch_bounds__(FUSED_THREADS) opnet_bwd_fused(const BwdArgs a
             if (t < T - 1)
                 rec = fused_product(a.w2bt + (long)tile * (H2 >> 2) * 64, a.g2 + (((long)(t + 1)) * a.RB + rb) * H2 * 32,
                                     H2 >> 2, hf, part);
+            else if (a.seeded && owner)
+                rec = a.dhpart2[e];
             if (owner) {
                 // upstream: prediction_layer (learned_models.py:47): dh += W_out^T dy_t
                 float dh = wo0 * dy.x;
@@ -548,7 +554,7 @@ __global__ void __launch_bounds__(FUSED_THREADS) opnet_bwd_fused(const BwdArgs a
                 for (int q = 0; q < 4; ++q) dlv[q] = dlp[q * 32];
 #pragma unroll
                 for (int o = 0; o < OPNET_SLOTS_; ++o) ws[o] = a.wsel[o * H1 + u];
-                if (t < T - 1) dcc = a.dc1[e];
+                if (t < T - 1 || a.seeded) dcc = a.dc1[e];
                 gs = a.g1[ge];
                 c_t = a.c1all[(((long)(t + 1)) * a.RB + rb) * H1 * 32 + (long)u * 32 + clip];
                 c_p = a.c1all[((long)t * a.RB + rb) * H1 * 32 + (long)u * 32 + clip];
@@ -557,6 +563,8 @@ __global__ void __launch_bounds__(FUSED_THREADS) opnet_bwd_fused(const BwdArgs a
             if (t < T - 1)
                 rec = fused_product(a.w1bt + (long)tile * (H1 >> 2) * 64, a.g1 + (((long)(t + 1)) * a.RB + rb) * H1 * 32,
                                     H1 >> 2, hf, part);
+            else if (a.seeded && owner)
+                rec = a.dhpart1[e];
             if (owner) {
                 // upstream: object_to_track_prediction (learned_models.py:40): dh += W_sel^T dl_t
                 float dh = 0.f;

@@ -85,6 +85,17 @@ def _extra_grad_operands(ctx, grad_y, grad_logits, dev):
     return grad_y, grad_logits, dboxes
 
 
+def _weight_grad_buffers(module, wshapes, dev):
+    """where a backward writes OPNet's six weight gradients: the slices of the module's gradient bucket when that is safe
+    (see _OPNetTrainFunction.backward), else fresh tensors"""
+    bucket = getattr(module, "_grad_bucket", None)
+    if bucket is not None and len(bucket.params) == len(wshapes) and bucket.flat.device == dev and \
+            all(tuple(p.shape) == s for p, s in zip(bucket.params, wshapes)) and \
+            all(p.grad is None for p in bucket.params):
+        return [bucket.view(i) for i in range(len(wshapes))]
+    return [torch.empty(s, dtype=torch.float32, device=dev) for s in wshapes]
+
+
 class _OPNetTrainFunction(torch.autograd.Function):
     """Autograd bridge: forward = opnet_train_forward_f32 (keeps the history in the module's training
     workspace), backward = opnet_train_backward_f32 (BPTT + weight-gradient GEMMs) - or opnet_train_backward_ex_f32 when a
@@ -133,13 +144,7 @@ class _OPNetTrainFunction(torch.autograd.Function):
         # - but only while no parameter holds a gradient: a p.grad that is still set (zero_grad(set_to_none=False), gradient
         # accumulation, a second backward) aliases the same slices after GradBucket.collect(), and AccumulateGrad would then
         # compute p.grad += new on aliased memory (2 x new instead of old + new)
-        bucket = getattr(module, "_grad_bucket", None)
-        if bucket is not None and len(bucket.params) == len(ctx.wshapes) and bucket.flat.device == dev and \
-                all(tuple(p.shape) == s for p, s in zip(bucket.params, ctx.wshapes)) and \
-                all(p.grad is None for p in bucket.params):
-            grads = [bucket.view(i) for i in range(len(ctx.wshapes))]
-        else:
-            grads = [torch.empty(s, dtype=torch.float32, device=dev) for s in ctx.wshapes]
+        grads = _weight_grad_buffers(module, ctx.wshapes, dev)
         tb = module._train
         with torch.cuda.device(dev):
             if grad_logits is None and dboxes is None:
@@ -223,13 +228,201 @@ class _OPNetMlpTrainFunction(torch.autograd.Function):
         return (None, dboxes, None, g_ih1, g_hh1, g_sel, g_hid4[:module._h2].contiguous(), g_out)
 
 
+# ------------------------------------------------------------------------------------------------
+# a forward from a carried state: OPNet and OPNetLstmMlp
+# ------------------------------------------------------------------------------------------------
+STATE_NAMES = ("h1", "c1", "h2", "c2")
+
+
+def check_state(state, B: int, h1: int, h2: int, mlp: bool, device) -> tuple:
+    """Validate `state` for a forward of B clips on `device`: a tuple (h1, c1, h2, c2) of float32 tensors [1, B, H1] /
+    [1, B, H2] in nn.LSTM's layout - what OPNetStreams.get_state returns - with h2 and c2 None for OPNetLstmMlp (mlp), which
+    has no video LSTM.  Returns the tuple; raises with the name of the offending operand.  Needs no GPU."""
+    if not isinstance(state, (tuple, list)) or len(state) != 4:
+        n = len(state) if isinstance(state, (tuple, list)) else type(state).__name__
+        raise ValueError(f"state must be a tuple (h1, c1, h2, c2) of 4 entries, got {n}")
+    device = torch.device(device)
+    for name, t, H in zip(STATE_NAMES, state, (h1, h1, h2, h2)):
+        video = name in ("h2", "c2")
+        if mlp and video:
+            if t is not None:
+                raise ValueError(f"state: OPNetLstmMlp has no video LSTM: {name} must be None")
+            continue
+        if t is None:
+            raise ValueError(f"state: {'OPNet needs h2 and c2: ' if video else ''}{name} must be a tensor, got None")
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"state: {name} must be a tensor, got {type(t).__name__}")
+        if tuple(t.shape) != (1, B, H):
+            raise ValueError(f"state: {name} must be [1, {B}, {H}], got {tuple(t.shape)}")
+        if t.dtype != torch.float32:
+            raise TypeError(f"state: {name} must be float32, got {t.dtype}")
+        if t.device.type != device.type or (device.index is not None and t.device.index is not None
+                                            and t.device.index != device.index):
+            raise ValueError(f"state: {name} is on {t.device}, the model on {device}")
+    return tuple(state)
+
+
+def _state_rows(state, B: int, h1: int, h2: int, dev) -> torch.Tensor:
+    """(h1, c1, h2, c2) -> rows [B, 2 H1 + 2 H2] = [h1 | c1 | h2 | c2], the C ABI's (and the stream pool's) layout; entries
+    that are None (OPNetLstmMlp's h2 / c2, an absent gradient) are zero columns"""
+    if all(t is not None for t in state):
+        return torch.cat([t[0] for t in state], dim=1)
+    rows = torch.zeros((B, 2 * h1 + 2 * h2), dtype=torch.float32, device=dev)
+    for t, lo, H in zip(state, (0, h1, 2 * h1, 2 * h1 + h2), (h1, h1, h2, h2)):
+        if t is not None:
+            rows[:, lo:lo + H] = t[0]
+    return rows
+
+
+def _rows_state(rows: torch.Tensor, h1: int, h2: int, mlp: bool) -> list:
+    """rows [B, 2 H1 + 2 H2] -> [h1, c1] (mlp) or [h1, c1, h2, c2], each [1, B, H], copies"""
+    cuts = ((0, h1), (h1, h1)) if mlp else ((0, h1), (h1, h1), (2 * h1, h2), (2 * h1 + h2, h2))
+    return [rows[:, lo:lo + H].unsqueeze(0).contiguous() for lo, H in cuts]
+
+
+class _OPNetStateTrainFunction(torch.autograd.Function):
+    """The training forward of OPNet / OPNetLstmMlp from a carried state (opnet_train_forward_state_f32: the launch chain at
+    every batch size, the state gathered into slot 0 of the history) and its backward (opnet_train_backward_state_f32): the
+    gradients arriving on the returned state seed the reverse recurrence, the state tensors that require grad get theirs.
+    Inputs (module, boxes, logits_grad, h1, c1, h2, c2, *weights), h2 / c2 None for OPNetLstmMlp; outputs y, logits and the
+    new h1, c1 (, h2, c2)."""
+
+    @staticmethod
+    def forward(ctx, module, boxes, logits_grad, h1s, c1s, h2s, c2s, *weights):
+        lib = _lib.load()
+        B, T = int(boxes.shape[0]), int(boxes.shape[1])
+        dev = boxes.device
+        h1, h2 = module._h1, module._h2
+        mlp = isinstance(module, OPNetLstmMlp)
+        with torch.cuda.device(dev):
+            stream = _stream_ptr(dev)
+            if mlp:
+                scratch = torch.empty(4 * h2 * 6, dtype=torch.float32, device=dev)
+                packed = module._train.packed(dev, (lib.opnet_train_packed_weights_bytes, h1, h2), lambda buf, n: _lib.check(
+                    lib.opnet_mlp_train_pack_weights_f32(*(w.data_ptr() for w in weights), buf.data_ptr(), n, scratch.data_ptr(),
+                                                         h1, h2, stream), "opnet_mlp_train_pack_weights_f32"), zero=True)
+            else:
+                packed = module._train.packed(dev, (lib.opnet_train_packed_weights_bytes, h1, h2), lambda buf, n: _lib.check(
+                    lib.opnet_train_pack_weights_f32(*(w.data_ptr() for w in weights), buf.data_ptr(), n, h1, h2, stream),
+                    "opnet_train_pack_weights_f32"))
+            tws = module._train.history_for(B, T, dev, (lib.opnet_train_workspace_bytes, B, T, h1, h2))
+            y = torch.empty((B, T, 4), dtype=torch.float32, device=dev)
+            logits = torch.empty((B, 15, T), dtype=torch.float32, device=dev)
+            rows_in = _state_rows((h1s, c1s, h2s, c2s), B, h1, h2, dev)
+            rows_out = torch.zeros_like(rows_in) if mlp else torch.empty_like(rows_in)
+            rc = lib.opnet_train_forward_state_f32(boxes.data_ptr(), packed.data_ptr(), y.data_ptr(), logits.data_ptr(),
+                                                   tws.data_ptr(), tws.numel(), B, T, h1, h2, int(mlp), rows_in.data_ptr(),
+                                                   rows_out.data_ptr(), stream)
+            _lib.check(rc, "opnet_train_forward_state_f32")
+            new_state = _rows_state(rows_out, h1, h2, mlp)
+        module._train_gen += 1
+        ctx.module, ctx.gen, ctx.shape, ctx.mlp = module, module._train_gen, (B, T), mlp
+        ctx.wshapes = [tuple(w.shape) for w in weights]
+        if not logits_grad:
+            ctx.mark_non_differentiable(logits)
+        ctx.set_materialize_grads(False)
+        return (y, logits, *new_state)
+
+    @staticmethod
+    def backward(ctx, grad_y, grad_logits, *grad_state):
+        module, mlp = ctx.module, ctx.mlp
+        if ctx.gen != module._train_gen:
+            raise RuntimeError(f"{type(module).__name__}: backward() after another training forward - the saved history of "
+                               "this forward has been overwritten (one history per module)")
+        n_in = 7 + len(ctx.wshapes)
+        grad_state = tuple(grad_state) + (None,) * (4 - len(grad_state))
+        if grad_y is None and grad_logits is None and all(g is None for g in grad_state):
+            return (None,) * n_in
+        lib = _lib.load()
+        B, T = ctx.shape
+        h1, h2 = module._h1, module._h2
+        dev = next(g for g in (grad_y, grad_logits) + grad_state if g is not None).device
+        grad_y, grad_logits, dboxes = _extra_grad_operands(ctx, grad_y, grad_logits, dev)
+        seed = None
+        if any(g is not None for g in grad_state):
+            seed = _state_rows(tuple(None if g is None else g.float() for g in grad_state), B, h1, h2, dev)
+        want = ctx.needs_input_grad[3:7]
+        dstate = torch.zeros((B, 2 * h1 + 2 * h2), dtype=torch.float32, device=dev) if any(want) else None
+        tb = module._train
+        if mlp:
+            g_ih1, g_hh1, g_sel, _, g_out = [torch.empty(s, dtype=torch.float32, device=dev) for s in ctx.wshapes]
+            g_hid4 = torch.empty((4 * h2, 6), dtype=torch.float32, device=dev)
+            gptrs = [g_ih1.data_ptr(), g_hh1.data_ptr(), g_sel.data_ptr(), g_hid4.data_ptr(), None, g_out.data_ptr()]
+        else:
+            grads = _weight_grad_buffers(module, ctx.wshapes, dev)
+            gptrs = [g.data_ptr() for g in grads]
+        with torch.cuda.device(dev):
+            extra = None
+            if grad_logits is not None or dboxes is not None:
+                extra = tb.extra_for(B, T, dev, (lib.opnet_train_extra_workspace_bytes, B, T, h1, h2))
+            rc = lib.opnet_train_backward_state_f32(grad_y.data_ptr(), tb.image.data_ptr(), tb.history.data_ptr(), tb.history.numel(),
+                                                    *gptrs, B, T, h1, h2, int(mlp),
+                                                    None if grad_logits is None else grad_logits.data_ptr(),
+                                                    None if dboxes is None else dboxes.data_ptr(),
+                                                    None if extra is None else extra.data_ptr(), 0 if extra is None else extra.numel(),
+                                                    None if seed is None else seed.data_ptr(),
+                                                    None if dstate is None else dstate.data_ptr(), _stream_ptr(dev))
+            _lib.check(rc, "opnet_train_backward_state_f32")
+            if mlp:
+                grads = [g_ih1, g_hh1, g_sel, g_hid4[:h2].contiguous(), g_out]
+            dst = [None] * 4
+            if dstate is not None:
+                for k, g in enumerate(_rows_state(dstate, h1, h2, mlp)):
+                    dst[k] = g if want[k] else None
+        return (None, dboxes, None, *dst) + tuple(grads)
+
+
+def _forward_from_state(module, boxes: torch.Tensor, logits_grad: bool, state, return_state: bool):
+    """model(boxes, state=..., return_state=...) of OPNet / OPNetLstmMlp: `boxes` checked, contiguous fp32"""
+    lib = _lib.load()
+    mlp = isinstance(module, OPNetLstmMlp)
+    B, T, dev = int(boxes.shape[0]), int(boxes.shape[1]), boxes.device
+    h1, h2 = module._h1, module._h2
+    state = module.zero_state(B) if state is None else check_state(state, B, h1, h2, mlp, dev)
+    ws = list(module._weights())
+    tensors = [t for t in state if t is not None]
+    if torch.is_grad_enabled() and (boxes.requires_grad or any(t.requires_grad for t in ws + tensors)):
+        check_weights(ws, dev, type(module).__name__)
+        y, logits, *new = _OPNetStateTrainFunction.apply(module, boxes, bool(logits_grad), *state, *ws)
+    else:
+        # inference: the stream step of the launch chain (opnet_stream_step_f32) over a private pool of B rows, row i = clip i
+        with torch.no_grad(), torch.cuda.device(dev):
+            stream = _stream_ptr(dev)
+            rows = _state_rows(state, B, h1, h2, dev)
+            slots = torch.arange(B, dtype=torch.int32, device=dev)
+            packed = module._packed_weights(dev)
+            sws = module._state_ws.get(stream, (B, T), dev, (lib.opnet_stream_workspace_bytes, B, T, h1, h2))
+            y = torch.empty((B, T, 4), dtype=torch.float32, device=dev)
+            logits = torch.empty((B, 15, T), dtype=torch.float32, device=dev)
+            _lib.check(lib.opnet_stream_step_f32(boxes.data_ptr(), slots.data_ptr(), rows.data_ptr(), packed.data_ptr(), y.data_ptr(),
+                                                 logits.data_ptr(), sws.data_ptr(), sws.numel(), B, T, B, h1, h2, int(mlp), stream),
+                       "opnet_stream_step_f32")
+            new = _rows_state(rows, h1, h2, mlp)
+    if not return_state:
+        return y, logits
+    return y, logits, (tuple(new) + (None, None) if mlp else tuple(new))
+
+
+def _zero_state(module, B: int) -> tuple:
+    dev = module.prediction_layer.weight.device
+    mk = lambda H: torch.zeros((1, int(B), H), dtype=torch.float32, device=dev)
+    if isinstance(module, OPNetLstmMlp):
+        return mk(module._h1), mk(module._h1), None, None
+    return mk(module._h1), mk(module._h1), mk(module._h2), mk(module._h2)
+
+
 class OPNet(AbstractCaterModel):
     """reference learned_models.py:18-52.  forward(boxes [B,T,15,6]) -> (y_boxes [B,T,4],
     object_to_track_prediction [B,15,T]).
 
     Training: the logits come back non-differentiable unless the forward is called with logits_grad=True (a loss on the
     selection, e.g. optim.selection_cross_entropy); `boxes` gets a gradient when it requires one.  Either runs the reverse
-    recurrence on the launch chain."""
+    recurrence on the launch chain.
+
+    State: forward(boxes, state=(h1, c1, h2, c2), return_state=True) -> (y, logits, new_state) starts from the given LSTM
+    state ([1, B, H] fp32 tensors: what OPNetStreams.get_state returns; None = zero) and returns the state after the last
+    frame.  In training the new state is differentiable and state tensors that require grad get gradients - truncated
+    BPTT, a learned initial state.  Either argument runs forward and reverse recurrence on the launch chain."""
 
     def __init__(self, config: Dict[str, int]):
         super().__init__(config)
@@ -262,6 +455,7 @@ class OPNet(AbstractCaterModel):
         self._x4ws = Workspaces(8)
         self._monitor = LaunchMonitor()      # abort words of the persistent launches (launch_monitor.py)
         self._train_aborted = False
+        self._state_ws = Workspaces(8)       # no_grad forwards from a state (opnet_stream_step_f32)
 
     # -- aborted persistent launches -------------------------------------------------------------
     def verify_launches(self) -> int:
@@ -419,7 +613,11 @@ class OPNet(AbstractCaterModel):
         return {k: ws[:12].view(torch.int32).tolist() for k, ws in self._xws.items()}
 
     # -- forward ------------------------------------------------------------------------------
-    def forward(self, boxes: torch.Tensor, logits_grad: bool = False):
+    def zero_state(self, B: int):
+        """(h1, c1, h2, c2) of B clips before their first frame: zeros [1, B, H] on the model's device"""
+        return _zero_state(self, B)
+
+    def forward(self, boxes: torch.Tensor, logits_grad: bool = False, state=None, return_state: bool = False):
         if not boxes.is_cuda:
             raise RuntimeError("objectpermanence_amd.OPNet runs on MI355X only: move `boxes` (and the model) "
                                "to a ROCm device; there is no CPU fallback")
@@ -427,6 +625,8 @@ class OPNet(AbstractCaterModel):
             raise ValueError(f"boxes must be [B, T, 15, 6], got {tuple(boxes.shape)}")
         lib = _lib.load()
         boxes = boxes.contiguous().float()
+        if state is not None or return_state:
+            return _forward_from_state(self, boxes, logits_grad, state, return_state)
         if torch.is_grad_enabled() and (boxes.requires_grad or any(w.requires_grad for w in self._weights())):
             ws = self._weights()
             check_weights(ws, boxes.device, "OPNet")
@@ -1078,10 +1278,15 @@ class OPNetLstmMlp(AbstractCaterModel):
         self._packed = PackedImages(8, "OPNetLstmMlp")
         self._ws = Workspaces(8)
         self._train, self._train_gen = TrainingBuffers(), 0
+        self._state_ws = Workspaces(8)       # no_grad forwards from a state (opnet_stream_step_f32)
 
     def _weights(self):
         return [self.object_to_track_LSTM.weight_ih_l0, self.object_to_track_LSTM.weight_hh_l0,
                 self.object_to_track_prediction.weight, self.hidden_layer.weight, self.prediction_layer.weight]
+
+    def zero_state(self, B: int):
+        """(h1, c1, None, None) of B clips before their first frame: zeros [1, B, H1] on the model's device"""
+        return _zero_state(self, B)
 
     def _packed_weights(self, device: torch.device) -> torch.Tensor:
         """the packed inference image (opnet_mlp_pack_weights_f32) for launches on the CURRENT stream (one per stream:
@@ -1094,11 +1299,13 @@ class OPNetLstmMlp(AbstractCaterModel):
                                     *(w.data_ptr() for w in ws_list), buf.data_ptr(), n, self._h1, self._h2, stream),
                                     "opnet_mlp_pack_weights_f32"), zero=True)
 
-    def forward(self, boxes: torch.Tensor, logits_grad: bool = False):
-        """logits_grad / boxes.requires_grad: as for OPNet"""
+    def forward(self, boxes: torch.Tensor, logits_grad: bool = False, state=None, return_state: bool = False):
+        """logits_grad / boxes.requires_grad / state / return_state: as for OPNet, with state = (h1, c1, None, None)"""
         _check_input(self, boxes, 6)
         lib = _lib.load()
         boxes = boxes.contiguous().float()
+        if state is not None or return_state:
+            return _forward_from_state(self, boxes, logits_grad, state, return_state)
         B, T, dev = int(boxes.shape[0]), int(boxes.shape[1]), boxes.device
         if _wants_grad(self) or (torch.is_grad_enabled() and boxes.requires_grad):
             ws_list = self._weights()

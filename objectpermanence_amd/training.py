@@ -13,7 +13,7 @@ from __future__ import annotations
 
 import math
 import warnings
-from typing import Optional
+from typing import Optional, Tuple, Union
 
 import torch
 import torch.distributed as dist
@@ -46,12 +46,17 @@ def train_step(model_name: str, model: torch.nn.Module, optimizer: torch.optim.O
                labels: Optional[torch.Tensor], mask: Optional[torch.Tensor] = None, group: Optional[dist.ProcessGroup] = None,
                n_global: Optional[int] = None, comm_stream: Optional[torch.cuda.Stream] = None,
                loss_kind: str = "l1", overlap=None, comm_events: Optional[list] = None,
-               selection_targets: Optional[torch.Tensor] = None, selection_weight: float = 1.0) -> torch.Tensor:
+               selection_targets: Optional[torch.Tensor] = None, selection_weight: float = 1.0,
+               state: Optional[tuple] = None) -> Union[torch.Tensor, Tuple[torch.Tensor, tuple]]:
     """zero_grad -> forward -> loss -> backward -> [gradient all-reduce] -> Adam (training_main.py:183-217).
 
     selection_targets [B, T] (int32 / int64 slot indices, -100 = no label; the double-output models only): supervises the
     selection head as well - loss = prediction loss + selection_weight * cross-entropy(logits, selection_targets), the
     backward started from both outputs at once.
+
+    state (h1, c1, h2, c2) (OPNet / OPNetLstmMlp: what model.zero_state(B), OPNetStreams.get_state or the previous call
+    returned): one chunk of truncated BPTT - the step starts from that LSTM state and the call returns (loss, new_state) with
+    new_state detached, the state to pass with the clips' next frames.  Without it the call returns the loss alone.
 
     Data parallel: EVERY rank calls this for every global batch - a rank whose slice of the batch is empty passes
     boxes=None, contributes zero gradients with weight 0 / n_global and still joins the collective and the optimiser step
@@ -62,6 +67,10 @@ def train_step(model_name: str, model: torch.nn.Module, optimizer: torch.optim.O
     runs on the current stream meanwhile, and only then does the current stream wait for the collective and run Adam."""
     if selection_targets is not None and model_name not in DOUBLE_OUTPUT_MODELS:
         raise ValueError(f"selection_targets: {model_name} has no selection logits")
+    if state is not None and not hasattr(model, "zero_state"):
+        raise ValueError(f"state: {model_name} takes no initial state (OPNet and OPNetLstmMlp do)")
+    state_kw = {} if state is None else {"state": state, "return_state": True}
+    new_state = state
     distributed = parallel.is_active(group)       # > 1 rank, or a forced group of one (OPNET_FORCE_DIST=1: the GPU tests)
     bucket = getattr(model, "_grad_bucket", None)
     if bucket is None:
@@ -70,7 +79,8 @@ def train_step(model_name: str, model: torch.nn.Module, optimizer: torch.optim.O
     n_local = 0 if boxes is None else int(boxes.shape[0])
     guard_word = None
     if n_local > 0 and selection_targets is not None:
-        output, logits = model(boxes, logits_grad=True)
+        output, logits, *rest = model(boxes, logits_grad=True, **state_kw)
+        new_state = rest[0] if rest else None
         if model_name in NO_LABELS_MODELS:
             pred, _, _ = compute_loss(model_name, output, labels, mask, loss_kind, with_consistency=False)
             (dy,) = torch.autograd.grad(pred, output, retain_graph=False)
@@ -82,8 +92,9 @@ def train_step(model_name: str, model: torch.nn.Module, optimizer: torch.optim.O
         torch.autograd.backward([output, logits], [dy, dlg * float(selection_weight)])
         guard_word = model.launch_guard() if hasattr(model, "launch_guard") else None
     elif n_local > 0:
-        out = model(boxes)
+        out = model(boxes, **state_kw)
         output = out[0] if model_name in DOUBLE_OUTPUT_MODELS else out
+        new_state = out[2] if state is not None else None
         if model_name not in NO_LABELS_MODELS and output.is_cuda:
             # supervised loss: value and gradient from one call, the backward started from dy (no autograd node for the loss)
             loss, dy = loss_and_grad(output, labels, 1.0 if loss_kind == "smooth_l1" else 0.0)
@@ -145,6 +156,8 @@ def train_step(model_name: str, model: torch.nn.Module, optimizer: torch.optim.O
         # train_step must not read memory that has been freed or reused since
         if hasattr(optimizer, "abort_ptr"):
             optimizer.abort_ptr = optimizer.loss_ptr = optimizer.guard_ptr = None
+    if state is not None:
+        return loss, tuple(None if t is None else t.detach() for t in new_state)
     return loss
 
 
