@@ -2,6 +2,7 @@
 // Plain pointers and sizes in, HIP launches on the caller's stream out; no torch types.
 #include "opnet_kernels.hip"
 #include "opnet_xcd_kernels.hip"
+#include "opnet_xcd_split_kernels.hip"
 #include "opnet_train_kernels.hip"
 #include "opnet_state_train_kernels.hip"
 #include "opnet_xcd4_kernels.hip"
@@ -363,6 +364,7 @@ extern "C" int opnet_forward_f32(const float *boxes, const float *packed, float 
 struct XcdWorkspaceLayout {  // offsets in bytes
     size_t status, flags, xp, h1h, h2h, fbh, yp, total;
     int NGT, ring, ho;
+    size_t wsp, xs, fbs;       // inference, head-once form: split weights, split planes of x, 2-KiB frames_boxes slots (opnet_xcd_split_kernels.hip)
 };
 
 // OPNET_XCD_RING (default 1): h1 / h2 / frames_boxes as rings of XCD_RING steps and the output head inside the launch (head-once
@@ -375,15 +377,22 @@ static int xcd_ring_mode() { return env_int("OPNET_XCD_RING", 1) != 0; }
 // critical path there and a lone head wave lengthens it: 88 k against 106 k clips/s at 256 clips, 68 k against 75 k at
 // 128; at 320 clips - XCDs with 3 and with 2 groups - 106 k against 93 k the other way).  OPNET_XCD_HO = 0 / 1 overrides.
 static int xcd_head_once(int NGT) { return env_int("OPNET_XCD_HO", (NGT + XCD_COUNT - 1) / XCD_COUNT >= 3 ? 1 : 0) != 0; }
+// the head-once inference forward with split-f16 products on the matrix pipe (opnet_xcd_forward_split);
+// OPNET_XCD_SPLIT=0: the exact-fp32 kernel everywhere
+static int xcd_split_mode() { return env_int("OPNET_XCD_SPLIT", 1) != 0; }
+// ... and with it the head-once form wins at every size: the products of a phase are 1 650 cycles instead of 6 700, so a lone head
+// wave no longer lengthens an exposed exchange by more than the other form's head on every CU costs (measured, 300 frames, ms
+// head-once split / every-CU-head fp32: 128 clips 1.08 / 1.71, 192: 1.96 / 2.28, 256: 1.95 / 2.39; tools/xcd_probe.py)
+static int xcd_head_once_split() { return env_int("OPNET_XCD_HO", 1) != 0; }
 
-static XcdWorkspaceLayout xcd_workspace_layout(int B, int T)
+static XcdWorkspaceLayout xcd_workspace_layout(int B, int T, bool infer = false)
 {
     XcdWorkspaceLayout L;
     const size_t NGT = (size_t)(B + 15) / 16;
     size_t o = 0;
     L.NGT = (int)NGT;
     L.ring = xcd_ring_mode();
-    L.ho = xcd_head_once(L.NGT);
+    L.ho = infer && xcd_split_mode() ? xcd_head_once_split() : xcd_head_once(L.NGT);
     const size_t NS = L.ring ? (size_t)XCD_RING : (size_t)(T + 1);
     L.status = o; o += 2048;                                   // 8 control words + 256 XCC ids
     L.flags = o;  o += align_up(NGT * XCD_CUS * 4, 256);
@@ -392,6 +401,14 @@ static XcdWorkspaceLayout xcd_workspace_layout(int B, int T)
     L.h2h = o;    o += NGT * NS * (XCD_H2 / 4) * 256;
     L.fbh = o;    o += NGT * NS * 1024;
     L.yp = o;     if (L.ring && !L.ho) o += NGT * (size_t)T * XCD_CUS * 256;
+    // behind everything the fp32 kernels use, whatever OPNET_XCD_SPLIT says: a workspace sized once serves both kernels
+    L.wsp = L.xs = L.fbs = 0;
+    if (infer && L.ho) {
+        o = align_up(o, 256);
+        L.wsp = o; o += align_up(packed_layout(XCD_H1, XCD_H2).total * 4, 256);
+        L.xs = o;  o += NGT * (size_t)(T + 2) * OPNET_KXQ * 256;
+        L.fbs = o; o += NGT * NS * 2048;
+    }
     L.total = align_up(o, 256);
     return L;
 }
@@ -406,7 +423,7 @@ static int check_xcd(int B, int T, int H1, int H2)
         return fail(OPNET_ESHAPE, "the per-XCD persistent forward is built for H1=%d, H2=%d (got %d, %d); use opnet_forward_f32",
                     XCD_H1, XCD_H2, H1, H2);
     if (B > XCD_MAX_B) return fail(OPNET_ESHAPE, "B=%d > %d clips per launch: split the batch", B, XCD_MAX_B);
-    const XcdWorkspaceLayout L = xcd_workspace_layout(B, T);
+    const XcdWorkspaceLayout L = xcd_workspace_layout(B, T, true);
     if (L.total >= ((size_t)1 << 31))
         return fail(OPNET_ESHAPE, "B=%d x T=%d: the workspace exceeds the 2 GiB one buffer descriptor addresses; split the batch", B, T);
     return OPNET_OK;
@@ -417,7 +434,7 @@ extern "C" int opnet_xcd_max_batch(void) { return XCD_MAX_B; }
 extern "C" size_t opnet_xcd_workspace_bytes(int B, int T, int H1, int H2)
 {
     if (check_xcd(B, T, H1, H2)) return 0;
-    return xcd_workspace_layout(B, T).total;
+    return xcd_workspace_layout(B, T, true).total;
 }
 
 // tools: in-kernel timeline of block 0 (device buffer of >= (T+1) * groups-per-XCD * 4 u64), null = off
@@ -606,6 +623,30 @@ static int xcd_forward_launch(const XcdSources &src, const XcdArgs &a, bool ho, 
     return OPNET_OK;
 }
 
+// the same for opnet_xcd_forward_split (head-once inference): the weights are split before every launch - they may have changed in
+// place - and that kernel also resets the status words, so it runs first
+static int xcd_forward_launch_split(const XcdSources &src, const XcdArgs &a0, const XcdWorkspaceLayout &L, int dev, hipStream_t st)
+{
+    XcdSplitArgs s;
+    memset(&s, 0, sizeof(s));
+    s.a = a0;
+    s.a.fbh = (float4 *)(a0.ws + L.fbs);
+    s.a.fb_off = (unsigned)L.fbs;
+    s.wsp = a0.ws + L.wsp;
+    s.xs_off = (unsigned)L.xs;
+    const PackedLayout P = packed_layout(XCD_H1, XCD_H2);
+    const long lanes = (long)((P.wih2p + (P.total - P.wselp)) / 512) * 64;
+    s.wsp_blocks = (unsigned)((lanes + 255) / 256);
+    opnet_xcd_split_weights<<<s.wsp_blocks, 256, 0, st>>>(s);
+    opnet_xcd_pack_input_split<<<dim3(s.a.T + 2, s.a.NGT), 384, 0, st>>>(src, s);
+    if (int rc = persistent_launch(dev, st, PROF_XCD, [&] { opnet_xcd_forward_split<<<XCD_COUNT * XCD_CUS, 512, 0, st>>>(s); }))
+        return rc;
+    if (s.a.ring) opnet_xcd_y_poison<<<64, 256, 0, st>>>(s.a, s.a.y);
+    else opnet_xcd_out_head_split<<<dim3(s.a.T, s.a.NGT), 256, 0, st>>>(s.a, s.a.y);
+    HIP_TRY(hipGetLastError());
+    return OPNET_OK;
+}
+
 static int xcd_forward_impl(const XcdSources &src, const float *packed, float *y, float *logits,
                             void *workspace, size_t workspace_bytes, int B, int T, int H1, int H2,
                             void *stream)
@@ -614,12 +655,13 @@ static int xcd_forward_impl(const XcdSources &src, const float *packed, float *y
     if (!packed || !y || !logits || !workspace) return fail(OPNET_EINVAL, "null pointer");
     if (!aligned16(packed) || !aligned16(y) || !aligned16(workspace))
         return fail(OPNET_EINVAL, "packed/y/workspace must be 16-byte aligned");
-    const XcdWorkspaceLayout L = xcd_workspace_layout(B, T);
+    const XcdWorkspaceLayout L = xcd_workspace_layout(B, T, true);
     if (workspace_bytes < L.total) return fail(OPNET_EWORKSPACE, "workspace %zu B < %zu B", workspace_bytes, L.total);
     int dev = 0;
     if (int rc = persistent_device(&dev)) return rc;
     XcdArgs a = make_xcd_args(L, 0, L.status, B, T, packed, (char *)workspace, y, logits);
     a.trace = g_xcd_trace;
+    if (L.ho && xcd_split_mode()) return xcd_forward_launch_split(src, a, L, dev, (hipStream_t)stream);
     return xcd_forward_launch<false>(src, a, L.ho, dev, (hipStream_t)stream);
 }
 

@@ -72,7 +72,7 @@ def main():
                  if "chain" in res else "") + f" | status {list(st.values())[-1]}", flush=True)
     if args.trace:
         lib = _lib.load()
-        for B in (128, 256, 384, 512, 640):
+        for B in (128, 256, 384, 512, 640, 1024):
             ng = (B + 127) // 128
             tr = torch.zeros((T + 4) * ng * 8, dtype=torch.int64, device=dev)
             lib.opnet_xcd_set_trace(tr.data_ptr())
