@@ -380,6 +380,9 @@ static int xcd_head_once(int NGT) { return env_int("OPNET_XCD_HO", (NGT + XCD_CO
 // the head-once inference forward with split-f16 products on the matrix pipe (opnet_xcd_forward_split);
 // OPNET_XCD_SPLIT=0: the exact-fp32 kernel everywhere
 static int xcd_split_mode() { return env_int("OPNET_XCD_SPLIT", 1) != 0; }
+// OPNET_XCD_PGATHER (default 1): in that kernel, with four or more groups on an XCD, the product waves issue the phase gather a finish
+// wave has found ready; 0: the finish waves issue every gather themselves (the A/B arm and the fallback)
+static int xcd_pgather_mode() { return env_int("OPNET_XCD_PGATHER", 1) != 0; }
 // ... and with it the head-once form wins at every size: the products of a phase are 1 650 cycles instead of 6 700, so a lone head
 // wave no longer lengthens an exposed exchange by more than the other form's head on every CU costs (measured, 300 frames, ms
 // head-once split / every-CU-head fp32: 128 clips 1.08 / 1.71, 192: 1.96 / 2.28, 256: 1.95 / 2.39; tools/xcd_probe.py)
@@ -634,6 +637,7 @@ static int xcd_forward_launch_split(const XcdSources &src, const XcdArgs &a0, co
     s.a.fb_off = (unsigned)L.fbs;
     s.wsp = a0.ws + L.wsp;
     s.xs_off = (unsigned)L.xs;
+    s.pgather = xcd_pgather_mode();
     const PackedLayout P = packed_layout(XCD_H1, XCD_H2);
     const long lanes = (long)((P.wih2p + (P.total - P.wselp)) / 512) * 64;
     s.wsp_blocks = (unsigned)((lanes + 255) / 256);

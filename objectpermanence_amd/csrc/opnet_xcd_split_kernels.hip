@@ -32,6 +32,16 @@
 //   LSTM2 gate: blocks 0..15 of h2, then the frames_boxes block.  LSTM1 gate = (blocks 0..5: x, h1[0..95]) + (blocks 6..10), each
 //   half its own fmaf(corr, 2^-11, main).  logits: blocks 0..7 on one wave.  y = ((w0 + w1) + w2) + w3 over the product waves, wave
 //   w blocks w, w+4, w+8, w+12.  frames_boxes: unchanged (fp32 einsum).
+//
+// Who issues the gather (four or more groups on the XCD; OPNET_XCD_PGATHER=0 restores the finish waves' early gather).  The 56 KiB of
+// LDS-DMA per phase block at issue on the full queue, ~1 720 cycles a phase, and used to sit in front of the finish wave's
+// head / cells / drain chain while the product wave of the same SIMD idled for 2 900 cycles.  Now finish wave 0, at the end of its
+// phase's work, looks ONCE at the 32 flags of the gather two barriers ahead and posts the verdict in sPG[parity]; both roles read
+// the word right after the barrier.  Ready: the product wave issues its first XS_PG_NP pieces behind its MFMA blocks and waits
+// vmcnt(0) before its barrier, the finish wave issues the rest and goes on.  Not ready: the finish waves poll and gather at the end
+// of the phase exactly as before (bounded spin, abort word) - product waves never look at global memory.  Never ready on the CU
+// whose finish wave 0 reads h1 for the selection head out of that buffer, nor where the product waves compute the output head
+// (2 phases in 32 per CU).  No arithmetic moves: y and logits are bit-identical (tests/test_opnet_xcd_pgather_gpu.py).
 #define XS_SCALE 2048.f
 #define XS_ISCALE (1.f / 2048.f)
 #define XS_RANGE 32768.f
@@ -52,6 +62,8 @@ struct XcdSplitArgs {
                                // the (unused) W_ih2 region holds one range word per block of opnet_xcd_split_weights
     unsigned xs_off;           // split planes of x in the workspace: [NGT][T+2][3 blocks][hi | lo][64 lanes][8 halfs]
     unsigned wsp_blocks;       // grid of opnet_xcd_split_weights
+    int pgather;               // OPNET_XCD_PGATHER (default 1): with four or more groups on an XCD the PRODUCT waves issue the phase
+                               // gather a finish wave has found ready; 0: the finish waves issue every gather themselves
 };
 
 __device__ __forceinline__ void xs_split(float v, _Float16 *hi, _Float16 *lo)
@@ -166,6 +178,60 @@ __device__ __forceinline__ void xs_store8(__amdgpu_buffer_rsrc_t r, unsigned vof
 
 #define XS_MFMA(a_, b_, c_) __builtin_amdgcn_mfma_f32_16x16x32_f16(a_, b_, c_, 0, 0, 0)
 
+// One wave's share (pieces w, w + 4, ...) of the gather of phase (group gi, step s) into LDS buffer `buf`: x = pieces 0..5,
+// h1 = 6..21, h2 = 22..53, frames_boxes = 54, 55.  The wave-uniform byte offsets, and piece 4 j + w by itself (j a constant after
+// unrolling) - the finish waves issue the 14 pieces in a row, the product waves one behind each block of their MFMAs.
+struct XsGather {
+    unsigned dst, ox0, oh1, oh2, ofb;
+};
+__device__ __forceinline__ XsGather xs_gather_of(const XcdSplitArgs &sa, unsigned lds0, unsigned g0, unsigned NS, unsigned smask, int gi, int s,
+                                                 int buf, int w)
+{
+    const XcdArgs &a = sa.a;
+    const int T = a.T;
+    const unsigned gg = g0 + gi;
+    XsGather o;
+    o.dst = lds0 + (unsigned)buf * (XS_F8 * 16) + w * 1024;
+    o.ox0 = sa.xs_off + ((gg * (T + 2) + (s < T ? s + 1 : T + 1)) * OPNET_KXQ) * 256 + w * 1024;
+    o.oh1 = a.h1_off + ((gg * NS + ((unsigned)(s <= T ? s : T) & smask)) * (XCD_H1 / 4)) * 256 + w * 1024;
+    o.oh2 = a.h2_off + ((gg * NS + ((unsigned)(s > 2 ? s - 2 : 0) & smask)) * (XCD_H2 / 4)) * 256 + w * 1024;
+    o.ofb = a.fb_off + (gg * NS + ((unsigned)(s > 1 ? s - 1 : 0) & smask)) * 2048 + w * 1024;
+    return o;
+}
+__device__ __forceinline__ void xs_gather_piece(__amdgpu_buffer_rsrc_t rws, unsigned lane16, const XsGather &o, int j, int w)
+{
+    // (each base holds + w KiB; the piece's place inside its region is a constant here, so that no "base - 22 KiB" lives in an SGPR)
+    const int q = 4 * j;
+    if (q + 3 < 6) xcd_glds16(rws, lane16, o.ox0 + q * 1024, o.dst + q * 1024);
+    else if (q >= 6 && q + 3 < 22) xcd_glds16(rws, lane16, o.oh1 + (q - 6) * 1024, o.dst + q * 1024);
+    else if (q >= 22 && q + 3 < 54) xcd_glds16(rws, lane16, o.oh2 + (q - 22) * 1024, o.dst + q * 1024);
+    else if (q + w < 6) xcd_glds16(rws, lane16, o.ox0 + q * 1024, o.dst + q * 1024);
+    else if (q + w < 22) xcd_glds16(rws, lane16, o.oh1 + (q - 6) * 1024, o.dst + q * 1024);
+    else if (q + w < 54) xcd_glds16(rws, lane16, o.oh2 + (q - 22) * 1024, o.dst + q * 1024);
+    else xcd_glds16(rws, lane16, o.ofb + (q - 54) * 1024, o.dst + q * 1024);
+}
+// a 32-bit kernel argument fetched where it is used (as XCD_KARG): what one finish wave in 128 needs per phase, or only a wait that
+// does not end at once, holds no SGPR across the finish waves' loop - the loop sits at the SGPR limit, and one spilled SGPR
+// reserves a VGPR for its lanes in the whole kernel, which the product waves' weights do not have
+template <unsigned OFF>
+__device__ __forceinline__ unsigned xs_karg_u32()
+{
+    unsigned v;
+    asm volatile("s_load_dword %0, %1, %2\n\ts_waitcnt lgkmcnt(0)" : "=s"(v) : "s"(__builtin_amdgcn_kernarg_segment_ptr()), "n"(OFF) : "memory");
+    return v;
+}
+#define XS_KARG32(field) xs_karg_u32<(unsigned)__builtin_offsetof(XcdArgs, field)>()
+// Of a wave's 14 pieces of a gather found ready, the product wave issues the first XS_PG_NP, one behind each of its first MFMA
+// blocks, and the finish wave of the same SIMD the rest right after the barrier.  Every issue blocks on the full DMA queue, in
+// whichever wave it sits: all 14 on the product wave and ITS chain bounds the phase (products + issue 3 340 cycles of a period of
+// 3 924 at 640 clips), 8 and both chains end together (period 3 552; 10: 3 556, 6: 3 692; all 14 up front, before the first MFMA:
+// 3 876 and the loop spills).  DESIGN.md section 3a.
+#ifndef XS_PG_NP
+#define XS_PG_NP 8
+#endif
+// wave-uniform condition bit of the finish waves' loop, beside XCD_CF_*: the product waves issue the gathers found ready
+#define XS_CF_PG 1024u
+
 // the persistent kernel, head-once form, inference: see opnet_xcd_forward for the roles and the protocol
 __global__ void __launch_bounds__(512, 2) opnet_xcd_forward_split(const XcdSplitArgs sa)
 {
@@ -176,6 +242,7 @@ __global__ void __launch_bounds__(512, 2) opnet_xcd_forward_split(const XcdSplit
     __shared__ float sC2[XCD_NGMAX][4][64];
     __shared__ float sC1[XCD_NGMAX][2][64];
     __shared__ int sAbort, sLocal, sH1done;
+    __shared__ int sPG[2];                    // [fp & 1]: the gather of phase fp + 2 is ready and the product waves issue it after barrier fp
     __shared__ unsigned sArrive[2];
 
     const int tid = threadIdx.x, lane = tid & 63;
@@ -207,6 +274,7 @@ __global__ void __launch_bounds__(512, 2) opnet_xcd_forward_split(const XcdSplit
             XCD_LDS_ST(sAbort, loc < 0);
             sArrive[0] = 0u; sArrive[1] = 0u;
             XCD_LDS_ST(sH1done, 0);
+            XCD_LDS_ST(sPG[0], 0); XCD_LDS_ST(sPG[1], 0);
             if (loc == 0 && c == 0) atomicAdd(a.status + 3, 1u);
         }
     }
@@ -236,6 +304,13 @@ __global__ void __launch_bounds__(512, 2) opnet_xcd_forward_split(const XcdSplit
                 if (q < 5 || !kh) { a1h[q] = p1[(2 * q) * 64]; a1l[q] = p1[(2 * q + 1) * 64]; }
                 else { a1h[q] = (xs_h8)(_Float16)0; a1l[q] = (xs_h8)(_Float16)0; }
             }
+            // The weights count as arrived HERE.  Left to the compiler, the waits for these loads sit in the product loop before each
+            // fragment's first MFMA (vmcnt(9) .. vmcnt(0)) - nothing to wait for after phase 0, until this wave has its own DMA in
+            // flight there: a vmcnt(0) in the fifth block would then wait out the first pieces of every phase's gather.
+#pragma unroll
+            for (int q = 0; q < 17; ++q) asm volatile("" :: "v"(a2h[q]), "v"(a2l[q]));
+#pragma unroll
+            for (int q = 0; q < 6; ++q) asm volatile("" :: "v"(a1h[q]), "v"(a1l[q]));
         }
         const bool mtracer = a.trace && blockIdx.x == 0 && tid == (4 - XCD_FW0) * 64;
         // output head: split A fragments of W_out (rows 0..3 of a 16-row tile), fetched on demand (once in 32 phases on a CU)
@@ -245,6 +320,14 @@ __global__ void __launch_bounds__(512, 2) opnet_xcd_forward_split(const XcdSplit
             const xcd_u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rwy, ylane, (unsigned)piece * 1024u, 0);
             return __builtin_bit_cast(xs_h8, v);
         };
+        // the gather of the NEXT phase, issued from here when a finish wave has found it ready (sPG; four or more groups): this
+        // wave's first XS_PG_NP pieces go out one behind each of the first blocks' MFMAs (the finish wave issues the rest).  The issue
+        // blocks on the full DMA queue - the per-CU L2 -> LDS floor is about the length of the products - and this wave used to idle
+        const bool pg = sa.pgather != 0 && ng >= 4;
+        const unsigned pNS = a.ring ? (unsigned)XCD_RING : (unsigned)(T + 1);
+        const unsigned psmask = a.ring ? (unsigned)(XCD_RING - 1) : 0xffffffffu;
+        const unsigned plds0 = (unsigned)(unsigned long long)(const void *)&sbuf[0][0];
+        const __amdgpu_buffer_rsrc_t prws = __builtin_amdgcn_make_buffer_rsrc((void *)a.ws, 0, 0x7fffffff, 0x00020000);
         __syncthreads();                        // phase 0's gather has landed
         if (XCD_LDS_LD(sAbort)) return;
         int pgi = 0, ps = 0;                    // phase p = ps * ng + pgi
@@ -254,6 +337,14 @@ __global__ void __launch_bounds__(512, 2) opnet_xcd_forward_split(const XcdSplit
             const xs_h8 *F2 = F + XS_H2;                    // h2 blocks 0..15, then the frames_boxes block
             const xs_h8 *FL = F + (kh ? 12 * 64 : 0);       // [x | h1] blocks 0..5 / 6..10
             if (mtracer) a.trace[(long)p * 8 + 0] = clock64();
+            // the verdict posted before barrier p - 1.  (After an abort the finish waves are gone and the word is stale: the
+            // phases run out on stale LDS as before, and the bound on p keeps a stale "ready" inside the workspace's slots.)
+            const bool issue = pg && !ycu && p >= 1 && p + 1 < nph && __builtin_amdgcn_readfirstlane(XCD_LDS_LD(sPG[(p - 1) & 1])) != 0;
+            XsGather go = {};
+            if (issue) {
+                const bool wrap = pgi + 1 == ng;
+                go = xs_gather_of(sa, plds0, g0, pNS, psmask, wrap ? 0 : pgi + 1, wrap ? ps + 1 : ps, (p + 1) & 1, w);
+            }
             f32x4 m2 = {0.f, 0.f, 0.f, 0.f}, c2 = m2, m1 = m2, c1 = m2;
             auto products = [&](auto yk) {
                 constexpr bool YK = decltype(yk)::value;    // this CU computes the output head in this phase
@@ -286,6 +377,9 @@ __global__ void __launch_bounds__(512, 2) opnet_xcd_forward_split(const XcdSplit
                         cy = XS_MFMA(ayl, bh[cur], cy);
                         if (j + 4 < 16) { ayh = yfrag(2 * j + 8); ayl = yfrag(2 * j + 9); }
                     }
+                    // (a wave-uniform branch, not a third variant of this loop: two more copies of it and the weights no longer stay put
+                    // in their registers.  The output head's variant has no register left for the DMA: its phases never issue.)
+                    if (!YK && j < XS_PG_NP && issue) xs_gather_piece(prws, ylane, go, j, w);
                     __builtin_amdgcn_sched_barrier(0);
                 }
                 if (YK)
@@ -293,13 +387,20 @@ __global__ void __launch_bounds__(512, 2) opnet_xcd_forward_split(const XcdSplit
                                                                     fmaf(cy[2], XS_ISCALE, my[2]), fmaf(cy[3], XS_ISCALE, my[3]));
             };
             if (ycu) products(std::true_type{});
-            else if (YH && ps == T + 2) {       // the extra step of the output head: nothing to do on the other CUs
+            else if (YH && ps == T + 2) {     // the extra step of the output head: nothing to compute on the other CUs
+                if (issue) {
+#pragma unroll
+                    for (int j = 0; j < XS_PG_NP; ++j) xs_gather_piece(prws, ylane, go, j, w);
+                }
             } else products(std::false_type{});
             if (mtracer) a.trace[(long)p * 8 + 1] = clock64();
             float4 *hd_ = &sHAND[p & 1][w][0] + lane;
             hd_[0] = make_float4(fmaf(c2[0], XS_ISCALE, m2[0]), fmaf(c2[1], XS_ISCALE, m2[1]), fmaf(c2[2], XS_ISCALE, m2[2]), fmaf(c2[3], XS_ISCALE, m2[3]));
             hd_[64] = make_float4(fmaf(c1[0], XS_ISCALE, m1[0]), fmaf(c1[1], XS_ISCALE, m1[1]), fmaf(c1[2], XS_ISCALE, m1[2]), fmaf(c1[3], XS_ISCALE, m1[3]));
-            // barrier p (no look at the abort word: see opnet_xcd_forward)
+            // barrier p (no look at the abort word: see opnet_xcd_forward); behind it the next phase reads what this wave gathered
+            if (issue) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            // (stamp 3 is this wave's when the launch gathers from here - the finish wave then leaves it alone; bit 0 = issued)
+            if (mtracer && pg) a.trace[(long)p * 8 + 3] = (clock64() & ~1ull) | (issue ? 1ull : 0ull);
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();
             asm volatile("" ::: "memory");
@@ -330,22 +431,9 @@ __global__ void __launch_bounds__(512, 2) opnet_xcd_forward_split(const XcdSplit
     // this wave's share (pieces w, w+4, ...) of the gather of phase (group gi, step s) into LDS buffer `buf`:
     // x = pieces 0..5, h1 = 6..21, h2 = 22..53, frames_boxes = 54, 55
     auto gather = [&](int gi, int s, int buf, int w) {
-        const unsigned gg = g0 + gi;
-        const unsigned dst = lds0 + (unsigned)buf * (XS_F8 * 16) + w * 1024;
-        const unsigned ox0 = sa.xs_off + ((gg * (T + 2) + (s < T ? s + 1 : T + 1)) * OPNET_KXQ) * 256 + w * 1024;
-        const unsigned oh1 = a.h1_off + ((gg * NS + ((unsigned)(s <= T ? s : T) & smask)) * (XCD_H1 / 4)) * 256 + (w - 6) * 1024;
-        const unsigned oh2 = a.h2_off + ((gg * NS + ((unsigned)(s > 2 ? s - 2 : 0) & smask)) * (XCD_H2 / 4)) * 256 + (w - 22) * 1024;
-        const unsigned ofb = a.fb_off + (gg * NS + ((unsigned)(s > 1 ? s - 1 : 0) & smask)) * 2048 + (w - 54) * 1024;
+        const XsGather o = xs_gather_of(sa, lds0, g0, NS, smask, gi, s, buf, w);
 #pragma unroll
-        for (int j = 0; j < XS_CHUNKS / 4; ++j) {
-            if (4 * j + 3 < 6) xcd_glds16(rws, lane16, ox0 + j * 4096, dst + j * 4096);
-            else if (4 * j >= 6 && 4 * j + 3 < 22) xcd_glds16(rws, lane16, oh1 + j * 4096, dst + j * 4096);
-            else if (4 * j >= 22 && 4 * j + 3 < 54) xcd_glds16(rws, lane16, oh2 + j * 4096, dst + j * 4096);
-            else if (4 * j + w < 6) xcd_glds16(rws, lane16, ox0 + j * 4096, dst + j * 4096);
-            else if (4 * j + w < 22) xcd_glds16(rws, lane16, oh1 + j * 4096, dst + j * 4096);
-            else if (4 * j + w < 54) xcd_glds16(rws, lane16, oh2 + j * 4096, dst + j * 4096);
-            else xcd_glds16(rws, lane16, ofb + j * 4096, dst + j * 4096);
-        }
+        for (int j = 0; j < XS_CHUNKS / 4; ++j) xs_gather_piece(rws, lane16, o, j, w);
     };
     auto flags_ready = [&](int gn, unsigned need) -> bool {
         const unsigned v = __builtin_amdgcn_raw_buffer_load_b32(rws, flag_voff, a.flags_off + (g0 + gn) * (XCD_CUS * 4), 16);   // sc1
@@ -354,7 +442,7 @@ __global__ void __launch_bounds__(512, 2) opnet_xcd_forward_split(const XcdSplit
     auto poll_gather = [&](int gn, int sn, int buf, int phase, int w, unsigned cf) {
         if (!alive || (cf & XCD_CF_DBG1)) return;
         if (sn > 0 && !flags_ready(gn, (unsigned)sn))
-            alive = xcd_wait_flags_ws(rws, a.flags_off + (g0 + gn) * (XCD_CUS * 4), (unsigned)sn, a.status_off, phase);
+            alive = xcd_wait_flags_ws(rws, a.flags_off + (g0 + gn) * (XCD_CUS * 4), (unsigned)sn, XS_KARG32(status_off), phase);
         if (alive) gather(gn, sn, buf, w);
         else XCD_LDS_ST(sAbort, 1);
     };
@@ -366,7 +454,7 @@ __global__ void __launch_bounds__(512, 2) opnet_xcd_forward_split(const XcdSplit
     if (XCD_LDS_LD(sAbort)) return;
     const unsigned cfbits = (ng >= 4 ? XCD_CF_NG4 : 0u) | (ng >= 2 ? XCD_CF_NG2 : 0u) | (ng == 1 ? XCD_CF_NG1 : 0u)
                             | ((a.debug & 1) ? XCD_CF_DBG1 : 0u) | ((a.debug & 2) ? XCD_CF_DBG2 : 0u) | ((a.debug & 4) ? XCD_CF_DBG4 : 0u)
-                            | ((a.debug & 8) ? XCD_CF_DBG8 : 0u) | (a.ring ? XCD_CF_RING : 0u)
+                            | ((a.debug & 8) ? XCD_CF_DBG8 : 0u) | (a.ring ? XCD_CF_RING : 0u) | (sa.pgather != 0 && ng >= 4 ? XS_CF_PG : 0u)
                             | (__builtin_amdgcn_readfirstlane(XCD_LDS_LD(sLocal)) != 0 ? XCD_CF_LOCAL : 0u)
                             | ((a.trace && blockIdx.x == 0 && wv == XCD_FW0) ? XCD_CF_TRACE : 0u);
 
@@ -387,7 +475,7 @@ __global__ void __launch_bounds__(512, 2) opnet_xcd_forward_split(const XcdSplit
         xcd_u32x4 xq[6];
         xs_h8 wsh[8], wsl[8];
         if (head_wave) {
-            const unsigned xs = a.xp_off + ((gg * (T + 2) + s) * OPNET_KXQ) * 256;
+            const unsigned xs = XS_KARG32(xp_off) + ((gg * (T + 2) + s) * OPNET_KXQ) * 256;
 #pragma unroll
             for (int j = 0; j < 6; ++j) xq[j] = __builtin_amdgcn_raw_buffer_load_b128(rws, xq_voff + j * 256, xs, 0);
             const xs_h8 *ps = (const xs_h8 *)((const char *)xcd_karg_u64<(unsigned)__builtin_offsetof(XcdSplitArgs, wsp)>() + P.wselp * 4) + lane;
@@ -400,11 +488,19 @@ __global__ void __launch_bounds__(512, 2) opnet_xcd_forward_split(const XcdSplit
         if (tracer) XCD_KARG(unsigned long long *, trace)[(long)fp * 8 + 2] = clock64();
         if (XCD_LDS_LD(sAbort)) return;
         bool early = false;
-        if ((cf & XCD_CF_NG4) && !head_cu && fp + 2 < nph && alive && !(cf & XCD_CF_DBG1) && (sn == 0 || flags_ready(gn, (unsigned)sn))) {
+        if (cf & XS_CF_PG) {
+            // the verdict wave 0 posted before this barrier: ready = the product waves issue the gather of phase fp + 2 right now
+            early = __builtin_amdgcn_readfirstlane(XCD_LDS_LD(sPG[fp & 1])) != 0;
+            if (XS_PG_NP < XS_CHUNKS / 4 && early) {
+                const XsGather o = xs_gather_of(sa, lds0, g0, NS, smask, gn, sn, fp & 1, wq);
+#pragma unroll
+                for (int j = XS_PG_NP; j < XS_CHUNKS / 4; ++j) xs_gather_piece(rws, lane16, o, j, wq);
+            }
+        } else if ((cf & XCD_CF_NG4) && !head_cu && fp + 2 < nph && alive && !(cf & XCD_CF_DBG1) && (sn == 0 || flags_ready(gn, (unsigned)sn))) {
             gather(gn, sn, fp & 1, wq);
             early = true;
         }
-        if (tracer) XCD_KARG(unsigned long long *, trace)[(long)fp * 8 + 3] = clock64();
+        if (tracer && !(cf & XS_CF_PG)) XCD_KARG(unsigned long long *, trace)[(long)fp * 8 + 3] = clock64();
 
         const float4 *H = &sHAND[fp & 1][0][0] + lane;
         // ---- selection head of step s-1: logits, softmax, einsum -> frames_boxes[s-1], which travels to every CU with this
@@ -433,7 +529,7 @@ __global__ void __launch_bounds__(512, 2) opnet_xcd_forward_split(const XcdSplit
             }
             {
                 float *lg = XCD_KARG(float *, logits) + ((long)gg * 16 * OPNET_SLOTS_) * T + (s - 1);
-                const bool clip_ok = (int)(gg * 16 + n) < a.B;
+                const bool clip_ok = (int)(gg * 16 + n) < (int)XS_KARG32(B);
 #pragma unroll
                 for (int r = 0; r < 4; ++r)
                     if (clip_ok && lg_voff[r] != 0xffffffffu) *(float *)((char *)lg + lg_voff[r]) = v[r];
@@ -530,7 +626,7 @@ __global__ void __launch_bounds__(512, 2) opnet_xcd_forward_split(const XcdSplit
             // output head of step s-3: the four product waves' K quarters in wave order; rows 0..3 = lanes 0..15 (clip = lane)
             const float4 p0 = H[0 * XH_F4 + 128], p1 = H[1 * XH_F4 + 128], p2 = H[2 * XH_F4 + 128], p3 = H[3 * XH_F4 + 128];
             const long b = (long)gg * 16 + lane;
-            if (lane < 16 && b < a.B)
+            if (lane < 16 && b < (long)(int)XS_KARG32(B))
                 XCD_KARG(float4 *, y)[b * T + (s - 3)] = make_float4(((p0.x + p1.x) + p2.x) + p3.x, ((p0.y + p1.y) + p2.y) + p3.y,
                                                                ((p0.z + p1.z) + p2.z) + p3.z, ((p0.w + p1.w) + p2.w) + p3.w);
         }
@@ -541,6 +637,21 @@ __global__ void __launch_bounds__(512, 2) opnet_xcd_forward_split(const XcdSplit
             }
             poll_gather(gn, sn, (fp + ahead) & 1, fp, wq, cf);
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        }
+        if ((cf & XS_CF_PG) && wq == 0) {
+            // The verdict for barrier fp + 1, in the time this wave used to wait for it: is the gather of phase fp + 3 ready?  One look
+            // at the 32 flags, never a spin - not ready, and the finish waves poll and gather it themselves at the end of the next
+            // phase (above), with the bounded spin and the abort word.  Never ready on the CU whose wave 0 reads h1 for the selection
+            // head out of the buffer that gather fills (sH1done), nor where the product waves then compute the output head (that variant of the
+            // product loop has no register left: it spills with the DMA in it) - 2 phases in 32 per CU stay with the finish waves.
+            int g1 = gi + 1, s1 = s, g2 = gi + 2, s2 = s, g3 = gi + 3, s3 = s;
+            if (g1 >= ng) { g1 -= ng; ++s1; }
+            if (g2 >= ng) { g2 -= ng; ++s2; }
+            if (g3 >= ng) { g3 -= ng; ++s3; }
+            bool ready = fp + 3 < nph && alive && !(cf & XCD_CF_DBG1) && !(xcd_head_cu(s1, g1) == c && s1 >= 1 && s1 <= T)
+                         && !((cf & XCD_CF_RING) && s2 >= 3 && xcd_y_cu(s2, g2) == c);
+            if (ready && s3 > 0) ready = flags_ready(g3, (unsigned)s3);
+            if (lane == 0) XCD_LDS_ST(sPG[(fp + 1) & 1], ready ? 1 : 0);
         }
         if (tracer) XCD_KARG(unsigned long long *, trace)[(long)fp * 8 + 7] = clock64();
         if (cf & XCD_CF_NG1) {

@@ -86,12 +86,26 @@ def main():
             t = tr.cpu().numpy().reshape(-1, 8)
             ph = t[len(t) // 3: 2 * len(t) // 3]
             med = lambda v: float(np.median(v))
-            print("B=%d (%d groups per XCD), cycles (median): period %.0f | product wave: products %.0f, hand-off + barrier wait %.0f | "
-                  "finish wave after the barrier: early-gather %.0f, head %.0f, cells %.0f, drain+flag %.0f, late poll+gather+land %.0f, "
-                  "to next barrier %.0f" % (
-                      B, ng, med(np.diff(ph[:, 0])), med(ph[:, 1] - ph[:, 0]), med(ph[1:, 0] - ph[:-1, 1]),
-                      med(ph[:, 3] - ph[:, 2]), med(ph[:, 4] - ph[:, 3]), med(ph[:, 5] - ph[:, 4]), med(ph[:, 6] - ph[:, 5]),
-                      med(ph[:, 7] - ph[:, 6]), med(ph[1:, 2] - ph[:-1, 7])))
+            # stamps of block 0: 0, 1 the product wave before / after its products; 2 the finish wave after the barrier, 4 after the
+            # head, 5 after the cells, 6 after drain + flag, 7 at the end of its phase.  Stamp 3 is the finish wave's (after its early
+            # gather) - except in launches whose product waves gather (split kernel, OPNET_XCD_PGATHER != 0, four or more groups on
+            # the XCD): there it is the product wave's, after its vmcnt wait, bit 0 = it issued the gather in that phase
+            pg = (ng >= 4 and os.environ.get("OPNET_XCD_PGATHER", "1") != "0" and os.environ.get("OPNET_XCD_SPLIT", "1") != "0"
+                  and os.environ.get("OPNET_XCD_HO", "1") != "0")
+            if pg:
+                print("B=%d (%d groups per XCD), cycles (median): period %.0f | product wave (gathers in %.1f %% of the phases): products + gather issue "
+                      "%.0f, vmcnt wait %.0f, hand-off + barrier wait %.0f | finish wave after the barrier: head %.0f, cells %.0f, drain+flag %.0f, "
+                      "readiness poll (+ late gather where not ready) %.0f, to next barrier %.0f" % (
+                          B, ng, med(np.diff(ph[:, 0])), 100.0 * float((ph[:, 3] & 1).mean()), med(ph[:, 1] - ph[:, 0]), med(ph[:, 3] - ph[:, 1]),
+                          med(ph[1:, 0] - ph[:-1, 3]), med(ph[:, 4] - ph[:, 2]), med(ph[:, 5] - ph[:, 4]), med(ph[:, 6] - ph[:, 5]),
+                          med(ph[:, 7] - ph[:, 6]), med(ph[1:, 2] - ph[:-1, 7])))
+            else:
+                print("B=%d (%d groups per XCD), cycles (median): period %.0f | product wave: products %.0f, hand-off + barrier wait %.0f | "
+                      "finish wave after the barrier: early-gather %.0f, head %.0f, cells %.0f, drain+flag %.0f, late poll+gather+land %.0f, "
+                      "to next barrier %.0f" % (
+                          B, ng, med(np.diff(ph[:, 0])), med(ph[:, 1] - ph[:, 0]), med(ph[1:, 0] - ph[:-1, 1]),
+                          med(ph[:, 3] - ph[:, 2]), med(ph[:, 4] - ph[:, 3]), med(ph[:, 5] - ph[:, 4]), med(ph[:, 6] - ph[:, 5]),
+                          med(ph[:, 7] - ph[:, 6]), med(ph[1:, 2] - ph[:-1, 7])))
             # block 0 = CU 0 of XCD 0: its phases by role (selection head / output head of the phase's step on this CU / neither)
             fp = np.arange(len(t))[len(t) // 3: 2 * len(t) // 3 - 1]
             gi, st_ = fp % ng, fp // ng
