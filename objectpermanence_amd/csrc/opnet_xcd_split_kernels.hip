@@ -229,6 +229,16 @@ __device__ __forceinline__ unsigned xs_karg_u32()
 #ifndef XS_PG_NP
 #define XS_PG_NP 8
 #endif
+// XS_ELOOK 1 (a measured variant, NOT the default: DESIGN_HISTORY.md section 7): finish wave 0 requests the flags for its NEXT verdict
+// right after posting this one, so that the load is in flight across the barrier and the value is read behind the vmcnt(0) of the next
+// drain; where it does not show all 32 flags the late look follows as without it.  Flags only grow, so what an earlier look saw is still
+// there, and the buffer a gather fills is released by the barrier, not by the look.  It does not pay: of the ~750 cycles the late look
+// takes on wave 0's chain only 130-250 are the load's round trip - the rest is the issue of the verdict's ~40 instructions behind the
+// product wave's MFMAs, where every instruction of a finish wave costs ~15 cycles, the early load's own among them.  0 compiles to the
+// kernel without it, instruction for instruction.
+#ifndef XS_ELOOK
+#define XS_ELOOK 0
+#endif
 // wave-uniform condition bit of the finish waves' loop, beside XCD_CF_*: the product waves issue the gathers found ready
 #define XS_CF_PG 1024u
 
@@ -459,6 +469,9 @@ __global__ void __launch_bounds__(512, 2) opnet_xcd_forward_split(const XcdSplit
                             | ((a.trace && blockIdx.x == 0 && wv == XCD_FW0) ? XCD_CF_TRACE : 0u);
 
     int gi = 0, s = 0;                          // phase fp = s * ng + gi
+#if XS_ELOOK
+    unsigned ev = 0u;                           // wave 0: the flags requested at the end of the phase before (0 passes for no step > 0)
+#endif
     for (int fp = 0; fp < nph; ++fp) {
         unsigned cf = __builtin_amdgcn_readfirstlane(cfbits);
         int wq = w;
@@ -614,7 +627,12 @@ __global__ void __launch_bounds__(512, 2) opnet_xcd_forward_split(const XcdSplit
         if (tracer) XCD_KARG(unsigned long long *, trace)[(long)fp * 8 + 5] = clock64();
         // ---- publish: every finish wave drains its stores (and DMA) and arrives at an LDS counter; the last one stores the
         //      CU's flag -------------------------------------------------------------------------------------------------------
+#if XS_ELOOK
+        // (ev is an operand so that its first use - and with it a wait for the early look - cannot be scheduled ahead of this wait)
+        asm volatile("s_waitcnt vmcnt(0)" : "+v"(ev) :: "memory");
+#else
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+#endif
         if (alive && !(cf & XCD_CF_DBG8)) {
             const bool last = (xcd_lds_add_lane0((unsigned)(unsigned long long)(const void *)&sArrive[fp & 1], 1u) & 3u) == 3u;
             if (last && lane == 0) {
@@ -650,8 +668,19 @@ __global__ void __launch_bounds__(512, 2) opnet_xcd_forward_split(const XcdSplit
             if (g3 >= ng) { g3 -= ng; ++s3; }
             bool ready = fp + 3 < nph && alive && !(cf & XCD_CF_DBG1) && !(xcd_head_cu(s1, g1) == c && s1 >= 1 && s1 <= T)
                          && !((cf & XCD_CF_RING) && s2 >= 3 && xcd_y_cu(s2, g2) == c);
+#if XS_ELOOK
+            // "ready" is only ever posted from a look that saw all 32 flags, and never less often than with the late look alone
+            if (ready && s3 > 0 && !__all(ev >= (unsigned)s3)) ready = flags_ready(g3, (unsigned)s3);
+            if (lane == 0) XCD_LDS_ST(sPG[(fp + 1) & 1], ready ? 1 : 0);
+            {
+                int g4 = g3 + 1;                // the group of the next verdict: always one of this XCD's, whatever the verdict will need
+                if (g4 >= ng) g4 = 0;
+                ev = __builtin_amdgcn_raw_buffer_load_b32(rws, flag_voff, a.flags_off + (g0 + g4) * (XCD_CUS * 4), 16);   // sc1
+            }
+#else
             if (ready && s3 > 0) ready = flags_ready(g3, (unsigned)s3);
             if (lane == 0) XCD_LDS_ST(sPG[(fp + 1) & 1], ready ? 1 : 0);
+#endif
         }
         if (tracer) XCD_KARG(unsigned long long *, trace)[(long)fp * 8 + 7] = clock64();
         if (cf & XCD_CF_NG1) {
