@@ -110,6 +110,10 @@ int opnet_xcd_profile_read(double *kernel_ms_total, int *launches);
 int opnet_kernel_profile_read(int tag, double *kernel_ms_total, int *launches);
 /* tools: device buffer of >= (T+1) * ceil(B/128) * 8 uint64 receiving s_memtime stamps of block 0 (NULL = off) */
 void opnet_xcd_set_trace(void *device_buffer);
+/* tests, tools (host only, reads the same environment as the launch): 1 when opnet_xcd_forward_f32 of B clips x T frames takes
+ * the steady-state instantiation of the split kernel - four or more 16-clip groups on every XCD, OPNET_XCD_RING / _SPLIT / _HO /
+ * _PGATHER on, OPNET_XCD_DEBUG = 0, OPNET_XCD_STEADY != 0 - else 0 (the general kernel; same results bit for bit) */
+int opnet_xcd_steady_form(int B, int T);
 /* ---- one small request as ONE persistent launch: groups of FOUR clips, one per XCD (csrc/opnet_xcd4_kernels.hip) -------------
  * The same function as opnet_forward_f32 for B <= opnet_xcd4_max_batch() clips (meant for B <= 64: the reference's inference
  * batch_size is 16, configs/inference_config.json:2, its training batch 32; row blocks of 32 clips run one after the other) at the reference hidden sizes on a whole MI355X

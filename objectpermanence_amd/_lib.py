@@ -54,6 +54,9 @@ def _declare(lib):
     lib.opnet_kernel_profile_read.argtypes = [c_int, POINTER(c_double), POINTER(c_int)]
     lib.opnet_xcd_set_trace.restype = None
     lib.opnet_xcd_set_trace.argtypes = [c_void_p]
+    if hasattr(lib, "opnet_xcd_steady_form"):      # additive entry, same ABI version: OPNET_HIP_LIB may name an older build (A/B arms)
+        lib.opnet_xcd_steady_form.restype = c_int
+        lib.opnet_xcd_steady_form.argtypes = [c_int, c_int]
     lib.opnet_xcd4_max_batch.restype = c_int
     lib.opnet_xcd4_max_batch.argtypes = []
     lib.opnet_xcd4_packed_weights_bytes.restype = c_size_t
@@ -357,7 +360,7 @@ EXPORTS = [
     "opnet_hip_abi_version", "opnet_last_error", "opnet_packed_weights_bytes", "opnet_pack_weights_f32",
     "opnet_workspace_bytes", "opnet_forward_f32", "opnet_plan_create", "opnet_plan_forward",
     "opnet_plan_destroy", "opnet_postprocess_iou", "opnet_encode_clips_f32", "opnet_load_clips_f32",
-    "opnet_xcd_max_batch", "opnet_xcd_supported", "opnet_xcd_workspace_bytes", "opnet_xcd_forward_f32", "opnet_xcd_forward_multi_f32", "opnet_xcd_set_trace", "opnet_xcd4_set_trace", "opnet_xcd4_last_status", "opnet_xcd4_max_batch", "opnet_xcd4_packed_weights_bytes",
+    "opnet_xcd_max_batch", "opnet_xcd_supported", "opnet_xcd_workspace_bytes", "opnet_xcd_forward_f32", "opnet_xcd_forward_multi_f32", "opnet_xcd_set_trace", "opnet_xcd_steady_form", "opnet_xcd4_set_trace", "opnet_xcd4_last_status", "opnet_xcd4_max_batch", "opnet_xcd4_packed_weights_bytes",
     "opnet_xcd4_workspace_bytes", "opnet_xcd4_pack_weights_f32", "opnet_xcd4_forward_f32",
     "opnet_xcd_profile", "opnet_xcd_profile_read", "opnet_kernel_profile_read",
     "opnet_train_packed_weights_bytes", "opnet_train_pack_weights_f32", "opnet_train_workspace_bytes",

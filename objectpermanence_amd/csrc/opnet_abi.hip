@@ -626,6 +626,23 @@ static int xcd_forward_launch(const XcdSources &src, const XcdArgs &a, bool ho, 
     return OPNET_OK;
 }
 
+// Which instantiation of the split kernel a launch takes (opnet_xcd_split_kernels.hip): the steady one has compiled in what a full
+// launch runs with - EVERY XCD carries four or more groups (xcd_groups hands XCD 7 the fewest), ring layout, product-wave gather,
+// no debug bit; a trace buffer picks its twin with the stamp sites.  OPNET_XCD_STEADY=0: the general kernel everywhere.
+static bool xcd_steady_form(const XcdWorkspaceLayout &L)
+{
+    int g0 = 0, ng_min = 0;
+    xcd_groups(L.NGT, XCD_COUNT - 1, &g0, &ng_min);
+    return ng_min >= 4 && L.ring && L.ho && xcd_split_mode() && xcd_pgather_mode() && env_int("OPNET_XCD_DEBUG", 0) == 0
+           && env_int("OPNET_XCD_STEADY", 1) != 0;
+}
+// tests, tools: 1 when an inference launch of B clips x T frames takes the steady kernel under the current environment (host only)
+extern "C" int opnet_xcd_steady_form(int B, int T)
+{
+    if (B < 1 || T < 1 || B > XCD_MAX_B) return 0;
+    return xcd_steady_form(xcd_workspace_layout(B, T, true)) ? 1 : 0;
+}
+
 // the same for opnet_xcd_forward_split (head-once inference): the weights are split before every launch - they may have changed in
 // place - and that kernel also resets the status words, so it runs first
 static int xcd_forward_launch_split(const XcdSources &src, const XcdArgs &a0, const XcdWorkspaceLayout &L, int dev, hipStream_t st)
@@ -643,7 +660,12 @@ static int xcd_forward_launch_split(const XcdSources &src, const XcdArgs &a0, co
     s.wsp_blocks = (unsigned)((lanes + 255) / 256);
     opnet_xcd_split_weights<<<s.wsp_blocks, 256, 0, st>>>(s);
     opnet_xcd_pack_input_split<<<dim3(s.a.T + 2, s.a.NGT), 384, 0, st>>>(src, s);
-    if (int rc = persistent_launch(dev, st, PROF_XCD, [&] { opnet_xcd_forward_split<<<XCD_COUNT * XCD_CUS, 512, 0, st>>>(s); }))
+    const bool steady = xcd_steady_form(L);
+    if (int rc = persistent_launch(dev, st, PROF_XCD, [&] {
+            if (steady && s.a.trace) opnet_xcd_forward_split<true, true><<<XCD_COUNT * XCD_CUS, 512, 0, st>>>(s);
+            else if (steady) opnet_xcd_forward_split<true, false><<<XCD_COUNT * XCD_CUS, 512, 0, st>>>(s);
+            else opnet_xcd_forward_split<false, true><<<XCD_COUNT * XCD_CUS, 512, 0, st>>>(s);
+        }))
         return rc;
     if (s.a.ring) opnet_xcd_y_poison<<<64, 256, 0, st>>>(s.a, s.a.y);
     else opnet_xcd_out_head_split<<<dim3(s.a.T, s.a.NGT), 256, 0, st>>>(s.a, s.a.y);

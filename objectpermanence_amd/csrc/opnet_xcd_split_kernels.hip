@@ -210,6 +210,56 @@ __device__ __forceinline__ void xs_gather_piece(__amdgpu_buffer_rsrc_t rws, unsi
     else if (q + w < 54) xcd_glds16(rws, lane16, o.oh2 + (q - 22) * 1024, o.dst + q * 1024);
     else xcd_glds16(rws, lane16, o.ofb + (q - 54) * 1024, o.dst + q * 1024);
 }
+// The steady kernel's gather (opnet_xcd_forward_split<true, .>).  A piece is 3 instructions instead of xcd_glds16's 7: m0 = dst + 4 j KiB,
+// soffset = base + 4 j KiB, the load.  m0 is neither saved nor restored - the compiler has no use for it in this kernel (no LDS-DMA
+// builtin, no s_movrel, no GWS: check the assembly after a change to the kernel) - and the second s_add is the wait state between
+// the write of m0 and the load that reads it.  No piece carries a region compare: base[r] is region r's offset MINUS the region's
+// first piece, so that piece q = 4 j + w reads base[r] + 4 j KiB whatever r is, and the three pieces whose region depends on the
+// wave (j = 1: x | h1, j = 5: h1 | h2, j = 13: h2 | frames_boxes) take their base from one select per gather (c1, c5, c13).
+struct XsGatherS {
+    unsigned dst, x, h1, h2, c1, c5, c13;
+};
+__device__ __forceinline__ XsGatherS xs_gather_steady_of(const XsGather &o, int w)
+{
+    XsGatherS g;
+    const bool hi = w >= 2;
+    g.dst = o.dst; g.x = o.ox0; g.h1 = o.oh1 - 6 * 1024; g.h2 = o.oh2 - 22 * 1024;
+    g.c1 = hi ? g.h1 : g.x;
+    g.c5 = hi ? g.h2 : g.h1;
+    g.c13 = hi ? o.ofb - 54 * 1024 : g.h2;
+    return g;
+}
+template <int J>
+__device__ __forceinline__ void xs_piece(__amdgpu_buffer_rsrc_t rsrc, unsigned voff, unsigned src, unsigned dst)
+{
+    if (J == 0) {
+        asm volatile("s_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, %2 offen sc1 lds"
+                     :: "v"(voff), "s"(rsrc), "s"(src), "s"(dst) : "memory");
+    } else {
+        unsigned t;
+        asm volatile("s_add_u32 m0, %4, %5\n\ts_add_u32 %0, %3, %5\n\tbuffer_load_dwordx4 %1, %2, %0 offen sc1 lds"
+                     : "=&s"(t) : "v"(voff), "s"(rsrc), "s"(src), "s"(dst), "n"(J * 4096) : "memory", "scc");
+    }
+}
+__device__ __forceinline__ void xs_gather_piece_steady(__amdgpu_buffer_rsrc_t rws, unsigned lane16, const XsGatherS &g, int j)
+{
+    switch (j) {                               // j is a constant after unrolling: one case survives
+    case 0: xs_piece<0>(rws, lane16, g.x, g.dst); break;
+    case 1: xs_piece<1>(rws, lane16, g.c1, g.dst); break;
+    case 2: xs_piece<2>(rws, lane16, g.h1, g.dst); break;
+    case 3: xs_piece<3>(rws, lane16, g.h1, g.dst); break;
+    case 4: xs_piece<4>(rws, lane16, g.h1, g.dst); break;
+    case 5: xs_piece<5>(rws, lane16, g.c5, g.dst); break;
+    case 6: xs_piece<6>(rws, lane16, g.h2, g.dst); break;
+    case 7: xs_piece<7>(rws, lane16, g.h2, g.dst); break;
+    case 8: xs_piece<8>(rws, lane16, g.h2, g.dst); break;
+    case 9: xs_piece<9>(rws, lane16, g.h2, g.dst); break;
+    case 10: xs_piece<10>(rws, lane16, g.h2, g.dst); break;
+    case 11: xs_piece<11>(rws, lane16, g.h2, g.dst); break;
+    case 12: xs_piece<12>(rws, lane16, g.h2, g.dst); break;
+    default: xs_piece<13>(rws, lane16, g.c13, g.dst); break;
+    }
+}
 // a 32-bit kernel argument fetched where it is used (as XCD_KARG): what one finish wave in 128 needs per phase, or only a wait that
 // does not end at once, holds no SGPR across the finish waves' loop - the loop sits at the SGPR limit, and one spilled SGPR
 // reserves a VGPR for its lanes in the whole kernel, which the product waves' weights do not have
@@ -239,10 +289,46 @@ __device__ __forceinline__ unsigned xs_karg_u32()
 #ifndef XS_ELOOK
 #define XS_ELOOK 0
 #endif
+// The steady kernel's finish wave issues its pieces XS_PG_NP .. 13 of a gather found ready as ONE statement (no pad between two
+// statements; m0 and the offset advance by 4 KiB a piece): pieces up to 12 lie in h2, 13 takes the wave's corner base.
+#if XS_PG_NP == 8
+#define XS_RUN_MIDS XS_RUN_MID XS_RUN_MID XS_RUN_MID XS_RUN_MID
+#elif XS_PG_NP == 7
+#define XS_RUN_MIDS XS_RUN_MID XS_RUN_MID XS_RUN_MID XS_RUN_MID XS_RUN_MID
+#elif XS_PG_NP == 6
+#define XS_RUN_MIDS XS_RUN_MID XS_RUN_MID XS_RUN_MID XS_RUN_MID XS_RUN_MID XS_RUN_MID
+#endif
+#define XS_RUN_LOAD "buffer_load_dwordx4 %1, %2, %0 offen sc1 lds\n\t"
+#define XS_RUN_MID "s_add_u32 m0, m0, 0x1000\n\ts_add_u32 %0, %0, 0x1000\n\t" XS_RUN_LOAD
+__device__ __forceinline__ void xs_gather_finish_run(__amdgpu_buffer_rsrc_t rws, unsigned lane16, const XsGatherS &g)
+{
+#ifdef XS_RUN_MIDS
+    unsigned t;
+    asm volatile("s_add_u32 m0, %5, %6\n\ts_add_u32 %0, %3, %6\n\t" XS_RUN_LOAD XS_RUN_MIDS
+                 "s_add_u32 m0, m0, 0x1000\n\ts_add_u32 %0, %4, %7\n\t" XS_RUN_LOAD
+                 : "=&s"(t) : "v"(lane16), "s"(rws), "s"(g.h2), "s"(g.c13), "s"(g.dst), "n"(XS_PG_NP * 4096), "n"(13 * 4096) : "memory", "scc");
+#else
+#pragma unroll
+    for (int j = XS_PG_NP; j < XS_CHUNKS / 4; ++j) xs_gather_piece_steady(rws, lane16, g, j);
+#endif
+}
 // wave-uniform condition bit of the finish waves' loop, beside XCD_CF_*: the product waves issue the gathers found ready
 #define XS_CF_PG 1024u
 
-// the persistent kernel, head-once form, inference: see opnet_xcd_forward for the roles and the protocol
+// the persistent kernel, head-once form, inference: see opnet_xcd_forward for the roles and the protocol.
+//
+// Three instantiations <STEADY, TRACE> (the kernel itself is the template: its body as an inlined function of a reference to the
+// arguments reads them through a generic pointer, and the general kernel then spills a weight fragment):
+//   <false, true>  general: every switch at run time, as ever
+//   <true, false>  steady: what a busy server and the benchmark run - four or more groups on EVERY XCD, ring layout, product-wave
+//                  gather, no debug bit, no trace buffer - all of that compiled in (the host routes: xcd_steady_form in opnet_abi.hip)
+//   <true, true>   steady with the stamp sites live, so that a trace measures the kernel that ships
+// STEADY removes instructions, never arithmetic: the finish chain is bound by instruction issue behind the product waves' MFMAs
+// (~15 cycles an instruction).  Gone from its loops: the stamp tests, the debug tests, the ng == 1 barrier, the
+// pre-pgather early-gather arm, the `ahead` / gn / sn loop, the multiplies of the ring offsets (NS = 4: shifts) and of the head-CU /
+// y-CU tests (a counter carried with the phase), and 4 of a DMA piece's 7 instructions.  The late path - poll with the bounded spin,
+// abort word, gather - the sH1done wait, the range refusal and the placement check are the same code in all three.
+template <bool STEADY, bool TRACE>
 __global__ void __launch_bounds__(512, 2) opnet_xcd_forward_split(const XcdSplitArgs sa)
 {
     const XcdArgs &a = sa.a;
@@ -268,7 +354,7 @@ __global__ void __launch_bounds__(512, 2) opnet_xcd_forward_split(const XcdSplit
     const int t2 = 4 * c + w;                 // LSTM2 tile of this SIMD
     const int t1 = 2 * c + (w >> 1), kh = w & 1;
     // steps 0 .. T+1 = LSTM1 step s | head step s-1 on ONE wave of the XCD | LSTM2 step s-2; ring mode: one more step for y[T-1]
-    const bool YH = a.ring != 0;
+    const bool YH = STEADY || a.ring != 0;
     const int nph = (YH ? T + 3 : T + 2) * ng;
     const PackedLayout P = packed_layout(XCD_H1, XCD_H2);
     if (wv == XCD_FW0) {
@@ -322,7 +408,7 @@ __global__ void __launch_bounds__(512, 2) opnet_xcd_forward_split(const XcdSplit
 #pragma unroll
             for (int q = 0; q < 6; ++q) asm volatile("" :: "v"(a1h[q]), "v"(a1l[q]));
         }
-        const bool mtracer = a.trace && blockIdx.x == 0 && tid == (4 - XCD_FW0) * 64;
+        const bool mtracer = TRACE && a.trace && blockIdx.x == 0 && tid == (4 - XCD_FW0) * 64;
         // output head: split A fragments of W_out (rows 0..3 of a 16-row tile), fetched on demand (once in 32 phases on a CU)
         const __amdgpu_buffer_rsrc_t rwy = __builtin_amdgcn_make_buffer_rsrc((void *)(sa.wsp + P.woutp * 4), 0, (XCD_H2 / 16) * 1024, 0x00020000);
         const unsigned ylane = lane * 16;
@@ -333,16 +419,19 @@ __global__ void __launch_bounds__(512, 2) opnet_xcd_forward_split(const XcdSplit
         // the gather of the NEXT phase, issued from here when a finish wave has found it ready (sPG; four or more groups): this
         // wave's first XS_PG_NP pieces go out one behind each of the first blocks' MFMAs (the finish wave issues the rest).  The issue
         // blocks on the full DMA queue - the per-CU L2 -> LDS floor is about the length of the products - and this wave used to idle
-        const bool pg = sa.pgather != 0 && ng >= 4;
-        const unsigned pNS = a.ring ? (unsigned)XCD_RING : (unsigned)(T + 1);
-        const unsigned psmask = a.ring ? (unsigned)(XCD_RING - 1) : 0xffffffffu;
+        const bool pg = STEADY || (sa.pgather != 0 && ng >= 4);
+        const unsigned pNS = STEADY || a.ring ? (unsigned)XCD_RING : (unsigned)(T + 1);
+        const unsigned psmask = STEADY || a.ring ? (unsigned)(XCD_RING - 1) : 0xffffffffu;
         const unsigned plds0 = (unsigned)(unsigned long long)(const void *)&sbuf[0][0];
         const __amdgpu_buffer_rsrc_t prws = __builtin_amdgcn_make_buffer_rsrc((void *)a.ws, 0, 0x7fffffff, 0x00020000);
         __syncthreads();                        // phase 0's gather has landed
         if (XCD_LDS_LD(sAbort)) return;
         int pgi = 0, ps = 0;                    // phase p = ps * ng + pgi
+        // steady: ps + 11 pgi, carried with the phase - xcd_y_cu(ps, pgi) = (pcu + 16) & 31 without the multiply
+        int pcu = 0;
+        const int pcu_wrap = 1 - 11 * (ng - 1);
         for (int p = 0; p < nph; ++p) {
-            const bool ycu = YH && ps >= 3 && xcd_y_cu(ps, pgi) == c;
+            const bool ycu = YH && ps >= 3 && (STEADY ? ((pcu + 16) & (XCD_CUS - 1)) : xcd_y_cu(ps, pgi)) == c;
             const xs_h8 *F = &sbuf[p & 1][0] + lane;
             const xs_h8 *F2 = F + XS_H2;                    // h2 blocks 0..15, then the frames_boxes block
             const xs_h8 *FL = F + (kh ? 12 * 64 : 0);       // [x | h1] blocks 0..5 / 6..10
@@ -351,9 +440,11 @@ __global__ void __launch_bounds__(512, 2) opnet_xcd_forward_split(const XcdSplit
             // phases run out on stale LDS as before, and the bound on p keeps a stale "ready" inside the workspace's slots.)
             const bool issue = pg && !ycu && p >= 1 && p + 1 < nph && __builtin_amdgcn_readfirstlane(XCD_LDS_LD(sPG[(p - 1) & 1])) != 0;
             XsGather go = {};
+            XsGatherS gs = {};
             if (issue) {
                 const bool wrap = pgi + 1 == ng;
                 go = xs_gather_of(sa, plds0, g0, pNS, psmask, wrap ? 0 : pgi + 1, wrap ? ps + 1 : ps, (p + 1) & 1, w);
+                if (STEADY) gs = xs_gather_steady_of(go, w);
             }
             f32x4 m2 = {0.f, 0.f, 0.f, 0.f}, c2 = m2, m1 = m2, c1 = m2;
             auto products = [&](auto yk) {
@@ -389,7 +480,10 @@ __global__ void __launch_bounds__(512, 2) opnet_xcd_forward_split(const XcdSplit
                     }
                     // (a wave-uniform branch, not a third variant of this loop: two more copies of it and the weights no longer stay put
                     // in their registers.  The output head's variant has no register left for the DMA: its phases never issue.)
-                    if (!YK && j < XS_PG_NP && issue) xs_gather_piece(prws, ylane, go, j, w);
+                    if (!YK && j < XS_PG_NP && issue) {
+                        if (STEADY) xs_gather_piece_steady(prws, ylane, gs, j);
+                        else xs_gather_piece(prws, ylane, go, j, w);
+                    }
                     __builtin_amdgcn_sched_barrier(0);
                 }
                 if (YK)
@@ -400,7 +494,10 @@ __global__ void __launch_bounds__(512, 2) opnet_xcd_forward_split(const XcdSplit
             else if (YH && ps == T + 2) {     // the extra step of the output head: nothing to compute on the other CUs
                 if (issue) {
 #pragma unroll
-                    for (int j = 0; j < XS_PG_NP; ++j) xs_gather_piece(prws, ylane, go, j, w);
+                    for (int j = 0; j < XS_PG_NP; ++j) {
+                        if (STEADY) xs_gather_piece_steady(prws, ylane, gs, j);
+                        else xs_gather_piece(prws, ylane, go, j, w);
+                    }
                 }
             } else products(std::false_type{});
             if (mtracer) a.trace[(long)p * 8 + 1] = clock64();
@@ -414,18 +511,19 @@ __global__ void __launch_bounds__(512, 2) opnet_xcd_forward_split(const XcdSplit
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();
             asm volatile("" ::: "memory");
-            if (ng == 1) {                      // exposed exchange: wait for this phase's finish + the next gather
+            if (!STEADY && ng == 1) {           // exposed exchange: wait for this phase's finish + the next gather
                 __builtin_amdgcn_s_barrier();
                 asm volatile("" ::: "memory");
             }
+            if (STEADY) pcu += pgi + 1 == ng ? pcu_wrap : 11;
             if (++pgi == ng) { pgi = 0; ++ps; }
         }
         return;
     }
 
     // ============================================== finish waves ======================================================
-    const unsigned NS = a.ring ? (unsigned)XCD_RING : (unsigned)(T + 1);
-    const unsigned smask = a.ring ? (unsigned)(XCD_RING - 1) : 0xffffffffu;
+    const unsigned NS = STEADY || a.ring ? (unsigned)XCD_RING : (unsigned)(T + 1);
+    const unsigned smask = STEADY || a.ring ? (unsigned)(XCD_RING - 1) : 0xffffffffu;
     const unsigned lds0 = (unsigned)(unsigned long long)(const void *)&sbuf[0][0];
     const __amdgpu_buffer_rsrc_t rws = __builtin_amdgcn_make_buffer_rsrc((void *)a.ws, 0, 0x7fffffff, 0x00020000);
     const unsigned lane16 = lane * 16;
@@ -466,9 +564,12 @@ __global__ void __launch_bounds__(512, 2) opnet_xcd_forward_split(const XcdSplit
                             | ((a.debug & 1) ? XCD_CF_DBG1 : 0u) | ((a.debug & 2) ? XCD_CF_DBG2 : 0u) | ((a.debug & 4) ? XCD_CF_DBG4 : 0u)
                             | ((a.debug & 8) ? XCD_CF_DBG8 : 0u) | (a.ring ? XCD_CF_RING : 0u) | (sa.pgather != 0 && ng >= 4 ? XS_CF_PG : 0u)
                             | (__builtin_amdgcn_readfirstlane(XCD_LDS_LD(sLocal)) != 0 ? XCD_CF_LOCAL : 0u)
-                            | ((a.trace && blockIdx.x == 0 && wv == XCD_FW0) ? XCD_CF_TRACE : 0u);
+                            | ((TRACE && a.trace && blockIdx.x == 0 && wv == XCD_FW0) ? XCD_CF_TRACE : 0u);
 
     int gi = 0, s = 0;                          // phase fp = s * ng + gi
+    // steady: s + 11 gi, carried with the phase - xcd_head_cu(s, gi) = fcu & 31 and xcd_y_cu(s, gi) = (fcu + 16) & 31 without the multiply
+    int fcu = 0;
+    const int fcu_wrap = 1 - 11 * (ng - 1);
 #if XS_ELOOK
     unsigned ev = 0u;                           // wave 0: the flags requested at the end of the phase before (0 passes for no step > 0)
 #endif
@@ -476,14 +577,18 @@ __global__ void __launch_bounds__(512, 2) opnet_xcd_forward_split(const XcdSplit
         unsigned cf = __builtin_amdgcn_readfirstlane(cfbits);
         int wq = w;
         asm volatile("" : "+s"(cf), "+s"(wq));
+        // steady: only the store form (and, with stamps, the tracer) is a run-time bit - every test of another bit folds away
+        if (STEADY) cf = (cf & (XCD_CF_LOCAL | (TRACE ? XCD_CF_TRACE : 0u))) | XCD_CF_NG4 | XCD_CF_NG2 | XCD_CF_RING | XS_CF_PG;
         const bool local = (cf & XCD_CF_LOCAL) != 0, tracer = (cf & XCD_CF_TRACE) != 0 && lane == 0;
         const unsigned gg = g0 + gi;
         const int ahead = (cf & XCD_CF_NG2) ? 2 : 1;
         int gn = gi + ahead, sn = s;
-        while (gn >= ng) { gn -= ng; ++sn; }
+        if (STEADY) { if (gn >= ng) { gn -= ng; ++sn; } }      // ahead = 2 < 4 <= ng: at most one wrap
+        else while (gn >= ng) { gn -= ng; ++sn; }
         // the selection head of step s-1: wave 0 of the step's head CU alone.  boxes[s-1] (fp32 image) and the 16 split A fragments
         // of W_sel are requested before the barrier, so that the round trips are over when the phase's sums arrive
-        const bool head_cu = xcd_head_cu(s, gi) == c && s >= 1 && s <= T;
+        const bool head_cu = (STEADY ? (fcu & (XCD_CUS - 1)) : xcd_head_cu(s, gi)) == c
+                             && (STEADY ? (unsigned)(s - 1) < (unsigned)T : (s >= 1 && s <= T));   // (one compare: the compiler keeps two and their masks)
         const bool head_wave = head_cu && wq == 0;
         xcd_u32x4 xq[6];
         xs_h8 wsh[8], wsl[8];
@@ -506,8 +611,12 @@ __global__ void __launch_bounds__(512, 2) opnet_xcd_forward_split(const XcdSplit
             early = __builtin_amdgcn_readfirstlane(XCD_LDS_LD(sPG[fp & 1])) != 0;
             if (XS_PG_NP < XS_CHUNKS / 4 && early) {
                 const XsGather o = xs_gather_of(sa, lds0, g0, NS, smask, gn, sn, fp & 1, wq);
+                if (STEADY) {
+                    xs_gather_finish_run(rws, lane16, xs_gather_steady_of(o, wq));
+                } else {
 #pragma unroll
-                for (int j = XS_PG_NP; j < XS_CHUNKS / 4; ++j) xs_gather_piece(rws, lane16, o, j, wq);
+                    for (int j = XS_PG_NP; j < XS_CHUNKS / 4; ++j) xs_gather_piece(rws, lane16, o, j, wq);
+                }
             }
         } else if ((cf & XCD_CF_NG4) && !head_cu && fp + 2 < nph && alive && !(cf & XCD_CF_DBG1) && (sn == 0 || flags_ready(gn, (unsigned)sn))) {
             gather(gn, sn, fp & 1, wq);
@@ -590,7 +699,7 @@ __global__ void __launch_bounds__(512, 2) opnet_xcd_forward_split(const XcdSplit
         }
         if (tracer) XCD_KARG(unsigned long long *, trace)[(long)fp * 8 + 4] = clock64();
         // ---- LSTM2 cell of step s-2: lane (clip n, unit 4 t2 + u); the gates arrive complete ----------------------------------
-        if (s >= 2 && s <= T + 1 && alive && !(cf & XCD_CF_DBG4)) {
+        if ((STEADY ? (unsigned)(s - 2) < (unsigned)T : (s >= 2 && s <= T + 1)) && alive && !(cf & XCD_CF_DBG4)) {
             const float4 g2 = H[w * XH_F4];
             float cc = sC2[gi][w][lane];
             const float h = lstm_cell(g2.x, g2.y, g2.z, g2.w, &cc);
@@ -640,7 +749,7 @@ __global__ void __launch_bounds__(512, 2) opnet_xcd_forward_split(const XcdSplit
                 else __builtin_amdgcn_raw_buffer_store_b32((unsigned)(s + 1), rws, 0, a.flags_off + (gg * XCD_CUS + c) * 4, 16);
             }
         }
-        if ((cf & XCD_CF_RING) && wq == 2 && s >= 3 && xcd_y_cu(s, gi) == c && alive && !(cf & XCD_CF_DBG4)) {
+        if ((cf & XCD_CF_RING) && wq == 2 && s >= 3 && (STEADY ? ((fcu + 16) & (XCD_CUS - 1)) : xcd_y_cu(s, gi)) == c && alive && !(cf & XCD_CF_DBG4)) {
             // output head of step s-3: the four product waves' K quarters in wave order; rows 0..3 = lanes 0..15 (clip = lane)
             const float4 p0 = H[0 * XH_F4 + 128], p1 = H[1 * XH_F4 + 128], p2 = H[2 * XH_F4 + 128], p3 = H[3 * XH_F4 + 128];
             const long b = (long)gg * 16 + lane;
@@ -666,8 +775,11 @@ __global__ void __launch_bounds__(512, 2) opnet_xcd_forward_split(const XcdSplit
             if (g1 >= ng) { g1 -= ng; ++s1; }
             if (g2 >= ng) { g2 -= ng; ++s2; }
             if (g3 >= ng) { g3 -= ng; ++s3; }
-            bool ready = fp + 3 < nph && alive && !(cf & XCD_CF_DBG1) && !(xcd_head_cu(s1, g1) == c && s1 >= 1 && s1 <= T)
-                         && !((cf & XCD_CF_RING) && s2 >= 3 && xcd_y_cu(s2, g2) == c);
+            // (steady: the carried counter one and two phases on; a wrap of the group adds fcu_wrap instead of 11)
+            const int hcu1 = STEADY ? ((fcu + (g1 == 0 ? fcu_wrap : 11)) & (XCD_CUS - 1)) : xcd_head_cu(s1, g1);
+            const int ycu2 = STEADY ? ((fcu + (g1 == 0 ? fcu_wrap : 11) + (g2 == 0 ? fcu_wrap : 11) + 16) & (XCD_CUS - 1)) : xcd_y_cu(s2, g2);
+            bool ready = fp + 3 < nph && alive && !(cf & XCD_CF_DBG1) && !(hcu1 == c && (STEADY ? (unsigned)(s1 - 1) < (unsigned)T : (s1 >= 1 && s1 <= T)))
+                         && !((cf & XCD_CF_RING) && s2 >= 3 && ycu2 == c);
 #if XS_ELOOK
             // "ready" is only ever posted from a look that saw all 32 flags, and never less often than with the late look alone
             if (ready && s3 > 0 && !__all(ev >= (unsigned)s3)) ready = flags_ready(g3, (unsigned)s3);
@@ -687,6 +799,7 @@ __global__ void __launch_bounds__(512, 2) opnet_xcd_forward_split(const XcdSplit
             __syncthreads();
             if (XCD_LDS_LD(sAbort)) return;
         }
+        if (STEADY) fcu += gi + 1 == ng ? fcu_wrap : 11;
         if (++gi == ng) { gi = 0; ++s; }
     }
 }

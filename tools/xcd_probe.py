@@ -42,7 +42,11 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--trace", action="store_true")
     ap.add_argument("--no-chain", action="store_true")
+    ap.add_argument("--general", action="store_true",
+                    help="OPNET_XCD_STEADY=0: the general instantiation of the split kernel where the steady one would run")
     args = ap.parse_args()
+    if args.general:
+        os.environ["OPNET_XCD_STEADY"] = "0"
     dev = torch.device("cuda:0")
     m = ModelsFactory.get_model("opnet", CFG)
     params = synth.opnet_synth_params(CFG)
@@ -92,6 +96,8 @@ def main():
             # the XCD): there it is the product wave's, after its vmcnt wait, bit 0 = it issued the gather in that phase
             pg = (ng >= 4 and os.environ.get("OPNET_XCD_PGATHER", "1") != "0" and os.environ.get("OPNET_XCD_SPLIT", "1") != "0"
                   and os.environ.get("OPNET_XCD_HO", "1") != "0")
+            steady = hasattr(lib, "opnet_xcd_steady_form") and lib.opnet_xcd_steady_form(B, T)      # (absent from an older OPNET_HIP_LIB)
+            print("B=%d: %s kernel" % (B, "steady (with stamps)" if steady else "general"))
             if pg:
                 print("B=%d (%d groups per XCD), cycles (median): period %.0f | product wave (gathers in %.1f %% of the phases): products + gather issue "
                       "%.0f, vmcnt wait %.0f, hand-off + barrier wait %.0f | finish wave after the barrier: head %.0f, cells %.0f, drain+flag %.0f, "
